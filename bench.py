@@ -15,8 +15,13 @@ batch's ids are bit-identical to a call on the batch alone (tests/test_engine.py
 config.ids_equal_one_batch_calls).  `one_call_alone` repeats the largest call shape on one context, `one_batch_in_flight` the
 one-batch-at-a-time loop of the reference.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+--dump-outputs DIR: after the timed regions, rank 0 writes what the last timed step handed its caller, as float64 .npy files
+(exact for token ids): ids.npy [batch, new_tokens + 1] (that batch's generate() ids on rank 0), gathered_ids.npy [batch x N, 512]
+and gathered_lengths.npy [batch x N] (the id exchange's all-gathered block of that step, pad-filled).  The inputs and weights are seeded, so
+two builds run with the same arguments can be compared array for array.
 
 Prints ONE JSON line on rank 0:
   roofline       dominant kernel (single-query cross-attention over the per-image K/V stream), algorithmic bytes / average
@@ -42,8 +47,6 @@ import time
 
 # before torch loads the HIP runtime: kernel arguments in device memory (see markushgrapher_amd/__init__.py)
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
-# one hardware queue per execution context of the batches in flight (same file)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 import numpy as np
 
@@ -51,8 +54,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 METRIC = "images/sec whole-node (greedy CXSMILES decode, 1024px crops, bs=32/GPU)"
-HBM_PEAK_GBS = 8000.0     # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
-MFMA_PEAK_TFLOPS = 2500.0  # dense bf16 MFMA (same guide)
+HBM_PEAK_GBS = 8000.0     # MI355X spec: HBM3E 8 TB/s
+MFMA_PEAK_TFLOPS = 2500.0  # MI355X spec: dense bf16 MFMA
 SOLO_STEPS = 3                                      # batches of the one-batch-in-flight side measurement
 EOS_ROW_SCALES = (3.0, 4.0, 6.0, 8.0, 12.0, 16.0)   # EOS-enabled run: ladder of scales of the EOS embedding row (see extra_runs)
 
@@ -299,6 +302,14 @@ def pmc_traffic(args, nb=1):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one float64 DIR/<name>.npy per array (token ids and lengths are exact in float64; 1 MB at 8 GPUs)."""
+    out = {k: v.cpu().numpy().astype(np.float64) for k, v in arrays.items()}
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
 def launcher_selftest(args, world, rank):
     """MG_BENCH_BACKEND=gloo (tests only, no GPU, NOT a measurement): the rank set-up of the multi-GPU run - environment from
     torch.distributed.run, process group, barrier, max-over-ranks reduction, the id exchange's all-gather on a stub payload - and one JSON
@@ -353,7 +364,11 @@ def main():
                          "by side in the decode step: the decoder's weights are read once per step for all of them); the `--steps` batches are "
                          "cut into near-equal calls so that every context is busy to the end; every image's ids are bit-identical to a call "
                          "on its batch alone (tests/test_engine.py::test_rows_do_not_depend_on_the_row_count)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float64; see the module docstring)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.pmc_child:
         return pmc_child(args)
     # `python bench.py --gpus N` started as ONE process (no torch.distributed.run around it): start the N ranks here - the same
@@ -566,6 +581,9 @@ def main():
         dts.append(dt)
         cpu_s.append((ru1.ru_utime - ru0.ru_utime) + (ru1.ru_stime - ru0.ru_stime))
     dt = float(np.median(dts))         # `value` = the median region
+    if args.dump_outputs and rank == 0:
+        # the exchange's receive block is reused by the next post: copied out here, before any side run
+        dump_outputs(args.dump_outputs, {"ids": ids, "gathered_ids": all_ids, "gathered_lengths": all_len})
     host_threads = threading.active_count()
     try:
         with open("/proc/self/status") as f_:

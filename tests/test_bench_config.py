@@ -401,3 +401,31 @@ def test_g4_greedy_kv_form_under_margin_rule():
             assert abs(top2[t, b, 0] - vals[b, t - 1, 0]) < LOGIT_TOL
             compared += 1
     assert compared >= 50
+
+
+def test_bench_dump_outputs_are_the_last_timed_step_and_repeat(tmp_path):
+    """`bench.py --dump-outputs DIR` on a small configuration (tiny shape, 3 steps over 2 contexts), run twice: both runs write the same
+    arrays (seeded inputs and weights), ids.npy is one batch of the step's width and the exchange's gathered block holds it, pad-filled."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    B, new, steps = 2, 6, 3
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--shape", "tiny", "--batch", str(B), "--new-tokens", str(new),
+                            "--steps", str(steps), "--warmup", "0", "--repeats", "1", "--inflight", "2", "--batches-per-call", "1",
+                            "--no-extra-runs", "--no-cpu-baseline", "--no-pmc", "--dump-outputs", str(d)],
+                           cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert out["steps"] == steps and sum(out["config"]["batches_per_call"]) == steps
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("ids", "gathered_ids", "gathered_lengths")})
+    for n in dumps[0]:
+        assert dumps[0][n].dtype == np.float64 and np.array_equal(dumps[0][n], dumps[1][n]), n
+    ids, g_ids, g_len = dumps[0]["ids"], dumps[0]["gathered_ids"], dumps[0]["gathered_lengths"]
+    assert ids.shape == (B, new + 1) and g_ids.shape == (B, 512) and g_len.shape == (B,)
+    assert np.array_equal(g_ids[:, :new + 1], ids) and (g_ids[:, new + 1:] == synth.SHAPES["tiny"].pad_token_id).all()
+    assert (g_len == new + 1).all()

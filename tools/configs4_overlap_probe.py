@@ -4,7 +4,6 @@ import os
 import sys
 
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 

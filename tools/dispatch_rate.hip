@@ -1,6 +1,6 @@
 // Probe: how many dependent kernel launches per second does the chip sustain on 1..6 streams (hardware queues) at once?
 // Each stream replays a captured chain of `len` kernels (grid x 512 threads, each spinning `spin` cycles).
-//   hipcc --offload-arch=gfx950 -O2 tools/dispatch_rate.hip -o /tmp/dispatch_rate && GPU_MAX_HW_QUEUES=8 /tmp/dispatch_rate
+//   hipcc --offload-arch=gfx950 -O2 tools/dispatch_rate.hip -o /tmp/dispatch_rate && /tmp/dispatch_rate
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <cstdio>

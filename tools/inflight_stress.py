@@ -5,7 +5,6 @@ import sys
 import traceback
 
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
