@@ -200,7 +200,7 @@ int mg_set_shared_gpu(mg_model* m, int shared);
  * (160 rows, 4 contexts in flight: 148 -> 197 images/s) and loses below (32 rows alone: 82 -> 50 images/s, latency-bound).
  *   absorb = 2 (default wherever the geometry has the form: d_model a supported multiple of 64, at most 16 heads): by the call's decode
  *              rows - absorbed from 96 rows on, K / V form below;
- *   absorb = 1: absorbed for every greedy call;   absorb = 0: the K / V form always (what beam search always uses);
+ *   absorb = 1: absorbed for every greedy call;   absorb = 0: the K / V form for every greedy call;
  *   absorb < 0: query only.
  * key_splits in 1..4: workgroups per decode row of the stream (0 keeps the setting).  The two forms round at different points (q' = q·Wk_h
  * and the normalised context are rounded to bf16 instead of K and V): logits agree within the stated tolerance, NOT bitwise - with
@@ -208,6 +208,15 @@ int mg_set_shared_gpu(mg_model* m, int shared);
  * reproducible across call sizes (markushgrapher_amd/inflight.py does, for the calls it packs).  Takes effect from the context's next
  * call.  Returns the previous `absorb`. */
 int mg_set_cross_absorb(mg_model* m, int absorb, int key_splits);
+/* Cross-attention of beam search (num_beams > 1: mg_generate and mg_generate_stream_beam, with or without the attached OCSR branch),
+ * independent of the greedy setting above.  absorb = 0 (default): the K / V form;  absorb = 1: the weight-absorbed form, in which one
+ * workgroup serves two (or three) beams of an image and every stage of the image's states is read once for all of them;  absorb < 0: query
+ * only.  key_splits in 1..4: workgroups per (image, beam subset) along the keys (0 keeps the setting; default 2).  Same rounding points and
+ * tolerance as the greedy absorbed form; a row's values do not depend on its sibling beams or batch mates.  The workspace sizes follow the
+ * setting (mg_workspace_bytes / mg_stream_beam_workspace_bytes).  Takes effect from the context's next call (its captured decode step and
+ * queue step are dropped); mg_clone copies it.  Returns the previous `absorb`; MG_E_UNSUPPORTED where the geometry has no absorbed form,
+ * MG_E_ARG for bad values. */
+int mg_set_beam_cross_absorb(mg_model* m, int absorb, int key_splits);
 /* 1 if the last mg_generate replayed a captured graph, 0 if it launched eagerly (mode 0/2, capture unavailable). */
 int mg_decode_graph_active(const mg_model* m);
 
@@ -306,6 +315,13 @@ int mgk_attention_step(void* stream, const void* q, const void* Kc, const void* 
  * each), qx (rows*H*d bf16), part (rows*nsplit*H*d bf16), ml (rows*nsplit*H*2 fp32); ctx_pk packed [rows padded to 32][H*64]. */
 int mgk_xattn(void* stream, const void* q, const float* wkv, const void* enc, const int* len, const int* kv_owner, int rows, int H, int d,
               int cap, int nsplit, int nstg, void* wk, void* wv, void* qx, void* part, float* ml, void* ctx_pk);
+/* The same for beam search (mg_set_beam_cross_absorb): rows = owners' images x group beams, row r attends owner
+ * kv_owner ? kv_owner[r / group] : r / group (kv_owner indexed by image); live [rows] nullable (rows with live == 0 are not written);
+ * beams_per_wg: beams of an image per workgroup (2, or 3 with nstg = 3 up to d = 768; 0 = the engine's choice); nt: 1 = the stream's
+ * copies carry the non-temporal hint (the engine's default), 0 = default cache policy. */
+int mgk_xattn_beams(void* stream, const void* q, const float* wkv, const void* enc, const int* len, const int* kv_owner, const int* live,
+                    int rows, int H, int d, int cap, int group, int nsplit, int nstg, int beams_per_wg, int nt, void* wk, void* wv, void* qx,
+                    void* part, float* ml, void* ctx_pk);
 int mgk_enc_rows(void* stream, const void* src_pk, const int* row_map, void* dst, int B, int rows_per_image, int cap, int d);
 int mgk_embed_assemble(void* stream, void* meta_ws, const int64_t* input_ids, const float* bbox,
                        const uint8_t* attention_mask, const float* patch_emb, const void* tok_emb, const void* x_emb,

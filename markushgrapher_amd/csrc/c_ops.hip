@@ -164,6 +164,25 @@ int mgk_xattn(void* stream, const void* q, const float* wkv, const void* enc, co
     xattn_contract(a, st);
     return MG_OK;
 }
+// The same for beam search (xattn_stream_beams): `group` rows per owner, kv_owner indexed by image, live [rows] nullable; beams_per_wg 0 =
+// the engine's choice; nt: cache policy of the stream's copies.
+int mgk_xattn_beams(void* stream, const void* q, const float* wkv, const void* enc, const int* len, const int* kv_owner, const int* live,
+                    int rows, int H, int d, int cap, int group, int nsplit, int nstg, int beams_per_wg, int nt, void* wk, void* wv, void* qx,
+                    void* part, float* ml, void* ctx_pk) {
+    if (!xattn_supported(d, H) || nsplit < 1 || nsplit > 4 || (nstg != 3 && nstg != 4)) return MG_E_UNSUPPORTED;
+    if (group < 1 || rows < group || rows % group != 0 || beams_per_wg < 0 || !xattn_beams_bp(d, nstg, beams_per_wg)) return MG_E_UNSUPPORTED;
+    mgStream_t st = (mgStream_t)stream;
+    xattn_pack_weights(wkv, (uint16_t*)wk, (uint16_t*)wv, H, d, st);
+    xattn_beams_prepare(d);
+    XAttnArgs a{};
+    a.q = (const uint16_t*)q; a.qx = (uint16_t*)qx; a.wk = (const uint16_t*)wk; a.wv = (const uint16_t*)wv; a.enc = (const uint16_t*)enc;
+    a.len = len; a.kv_owner = kv_owner; a.live = live; a.part = (uint16_t*)part; a.ml = ml; a.ctx = (uint16_t*)ctx_pk;
+    a.rows = rows; a.H = H; a.d = d; a.cap = cap; a.nsplit = nsplit; a.nstg = nstg; a.nt = nt ? 1 : 0; a.group = group; a.bpw = beams_per_wg;
+    xattn_expand(a, st);
+    xattn_stream_beams(a, st);
+    xattn_contract(a, st);
+    return MG_OK;
+}
 // rows of a packed [B*rows_per_image][d] bf16 operand -> natural rows dst[b][row_map[r]][d] (k_xattn.hip enc_rows)
 int mgk_enc_rows(void* stream, const void* src_pk, const int* row_map, void* dst, int B, int rows_per_image, int cap, int d) {
     enc_rows((const uint16_t*)src_pk, row_map, (uint16_t*)dst, B, rows_per_image, cap, d, (mgStream_t)stream);

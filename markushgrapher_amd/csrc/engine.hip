@@ -40,6 +40,7 @@ size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 int round_up(int x, int a) { return (x + a - 1) / a * a; }
 constexpr int MG_ABSORB_AUTO_ROWS = 96;
 bool use_absorb(const mg_model* m, int K, int rows);
+int xa_nsplit(const mg_model* m, int K);
 
 struct EncLayer { size_t wqkv, wo, ln0, wi, wo2, ln1; };
 // xq2 / wi2: product weights of the decode step (built by mg_finalize): [Wxq·G1 | Wxq·G1·Wo] and [Wi·G2 | Wi·G2·Wxo]
@@ -104,8 +105,12 @@ struct mg_model {
     bool graph_active = false;
     // Greedy decoding with the weight-absorbed cross-attention (k_xattn.hip): a layer streams the encoder states once instead of its K and V.
     // absorb: 2 (default where the geometry is supported) = by the call's decode rows (>= 96: absorbed), 1: every greedy call, 0: the K / V form for
-    // every call (mg_set_cross_absorb, MG_XATTN_ABSORB).  Beam search keeps the K / V form.
+    // every call (mg_set_cross_absorb, MG_XATTN_ABSORB).  Beam search: beam_absorb (mg_set_beam_cross_absorb) - 0 (default) the K / V form,
+    // 1 the absorbed form with the beams of an image sharing each stage (xattn_stream_beams) and its own key splits xb_split.
     int xa_nt = 1;           // the stream's copies carry the non-temporal hint (states read once per layer by one CU must not displace the weights in L2 / MALL: +5 % in flight; MG_XATTN_NT=0)
+    // (beam form: key splits 2 and the default cache policy for the stream's copies - measured fastest at d 1024, 160 rows: 59 -> 53 us per
+    // launch against the non-temporal hint; profiles/r07_beam_cross_absorb.txt)
+    int beam_absorb = 0, xb_split = 2, xb_nt = 0;
     int absorb = 2, xa_split = 1, xa_stages = 4;      // (xa_stages: 4 = two wave groups, 136 KB of LDS: equal in flight, faster alone; 3 = one group, 100 KB - a decode projection's workgroup fits beside it on the CU)
     int shared_gpu = 0;       // mg_set_shared_gpu: other contexts run beside this one (the cross-attention stream keeps one workgroup per CU resident)
     // optional phase timing of mg_generate (HIP events): [start, encoder + cross-K/V done, decode loop done]
@@ -365,8 +370,8 @@ void carve(const mg_model* m, char* base, int B, int L, int K, int max_len, int 
         if (use_absorb(m, K, R)) {
             w->encx = c.take<uint16_t>((size_t)B * Sx_cap * d);
             w->qx = c.take<uint16_t>((size_t)Rp * H * d);
-            w->xpart = c.take<uint16_t>((size_t)Rp * m->xa_split * H * d);
-            w->xml = c.take<float>((size_t)Rp * m->xa_split * H * 2);
+            w->xpart = c.take<uint16_t>((size_t)Rp * xa_nsplit(m, K) * H * d);
+            w->xml = c.take<float>((size_t)Rp * xa_nsplit(m, K) * H * 2);
         } else {
             w->xk = c.take<uint16_t>(nl * B * H * Sx_cap * 64);
             w->xv = c.take<uint16_t>(nl * B * H * Sx_cap * 64);
@@ -456,8 +461,8 @@ void carve_stream(const mg_model* m, char* base, int chunk, int L, int slots_img
     if (use_absorb(m, K, slots)) {
         w->encx = c.take<uint16_t>(entries * Sx_cap * d);
         w->qx = c.take<uint16_t>((size_t)Rp * H * d);
-        w->xpart = c.take<uint16_t>((size_t)Rp * m->xa_split * H * d);
-        w->xml = c.take<float>((size_t)Rp * m->xa_split * H * 2);
+        w->xpart = c.take<uint16_t>((size_t)Rp * xa_nsplit(m, K) * H * d);
+        w->xml = c.take<float>((size_t)Rp * xa_nsplit(m, K) * H * 2);
     } else {
         w->xk = c.take<uint16_t>(nl * w->pool_stride);
         w->xv = c.take<uint16_t>(nl * w->pool_stride);
@@ -530,8 +535,13 @@ __global__ __launch_bounds__(64) void stream_ready_kernel(int n, int* ctr) {
 }
 
 // greedy calls stream the encoder states (k_xattn.hip); beam search keeps the per-layer K / V streams (its G rows of an image share one pass)
+// unless the beam setting is on (mg_set_beam_cross_absorb: the beams of an image then share each stage of the states' stream)
 // (auto: from 96 decode rows on - below that the stream's one workgroup per row is latency-bound and the K / V form's 16 workgroups per row win)
-bool use_absorb(const mg_model* m, int K, int rows) { return K == 1 && (m->absorb == 1 || (m->absorb == 2 && rows >= MG_ABSORB_AUTO_ROWS)); }
+bool use_absorb(const mg_model* m, int K, int rows) {
+    if (K > 1) return m->beam_absorb == 1;
+    return m->absorb == 1 || (m->absorb == 2 && rows >= MG_ABSORB_AUTO_ROWS);
+}
+int xa_nsplit(const mg_model* m, int K) { return K > 1 ? m->xb_split : m->xa_split; }      // key splits of the absorbed stream
 
 int check_launch(const char* what) {
     const int e = mg_peek_error();
@@ -704,11 +714,13 @@ static void decode_step(mg_model* m, const DecodeCtx& c, int t, const int* tdev,
         if (c.encx) {      // weight-absorbed form: q' = q·Wk_h | stream of the states | ctx_h = c_h·Wv_h^T   (the bracket times the stream)
             xa.q = c.dq; xa.qx = c.qx; xa.wk = m->at<uint16_t>(l.xwk); xa.wv = m->at<uint16_t>(l.xwv); xa.enc = c.encx; xa.len = c.xlen;
             xa.kv_owner = c.slots.pool; xa.live = live; xa.qrs = rs1; xa.part = c.xpart; xa.ml = c.xml; xa.ctx = c.xb; xa.ctx_ld = K2; xa.ctx_col0 = d;
-            xa.rows = R; xa.H = H; xa.d = d; xa.cap = Sx_cap; xa.nsplit = m->xa_split; xa.nstg = m->xa_stages; xa.nt = m->xa_nt;
+            xa.rows = R; xa.H = H; xa.d = d; xa.cap = Sx_cap; xa.nsplit = xa_nsplit(m, K); xa.nstg = m->xa_stages; xa.nt = m->xa_nt;
+            xa.group = K;
+            if (K > 1) { xa.kv_owner = stream ? c.bpool : nullptr; xa.nt = m->xb_nt; }      // beams: one owner per image (slot) of K rows
             if (!(whatif & 8)) xattn_expand(xa, st);
         }
         if (timed) mg_event_record(m->prof_ev[m->prof_used], st);
-        if (!(whatif & 8)) { if (c.encx) xattn_stream(xa, st); else attention_step(x, st); }
+        if (!(whatif & 8)) { if (c.encx) { if (K > 1) xattn_stream_beams(xa, st); else xattn_stream(xa, st); } else attention_step(x, st); }
         if (timed) {   // third event right behind the second: the empty bracket calibrates what two records alone cost
             mg_event_record(m->prof_ev[m->prof_used + 1], st);
             mg_event_record(m->prof_ev[m->prof_used + 2], st);
@@ -880,7 +892,7 @@ int mg_clone(const mg_model* src, mg_model** out) {
     m->fin_a = src->fin_a; m->fin_b = src->fin_b; m->fin_c = src->fin_c;
     m->use_graph = src->use_graph; m->enc_mode = src->enc_mode; m->enc_mask = src->enc_mask;
     m->row_tiles = src->row_tiles; m->trim_padding = src->trim_padding; m->fused_tail = src->fused_tail; m->tied = src->tied;
-    m->absorb = src->absorb; m->xa_split = src->xa_split; m->xa_stages = src->xa_stages; m->pace = src->pace; m->xa_nt = src->xa_nt;
+    m->absorb = src->absorb; m->xa_split = src->xa_split; m->beam_absorb = src->beam_absorb; m->xb_split = src->xb_split; m->xb_nt = src->xb_nt; m->xa_stages = src->xa_stages; m->pace = src->pace; m->xa_nt = src->xa_nt;
     m->e1m = src->e1m; m->e1_M = src->e1_M;
     *out = m;
     return MG_OK;
@@ -1089,7 +1101,7 @@ int mg_finalize(mg_model* m, void* stream) {
                 xattn_pack_weights(A, m->at<uint16_t>(l.xwk), m->at<uint16_t>(l.xwv), m->H, d, st);
             }
         }
-        if (xattn_supported(d, m->H)) { xattn_stream_prepare(d, 4); xattn_stream_prepare(d, 3); }
+        if (xattn_supported(d, m->H)) { xattn_stream_prepare(d, 4); xattn_stream_prepare(d, 3); xattn_beams_prepare(d); }
     }
     mg_stream_sync(st);    // the host tables above must outlive the copies
     const int rc = check_launch("mg_finalize");
@@ -1850,6 +1862,19 @@ int mg_set_cross_absorb(mg_model* m, int absorb, int key_splits) {
     if (absorb && !xattn_supported(m->d, m->H)) return fail(MG_E_UNSUPPORTED, "mg_set_cross_absorb: d_model %d / %d heads have no absorbed form", m->d, m->H);
     m->absorb = absorb;
     if (key_splits) m->xa_split = key_splits;
+    m->step_graph.reset(); m->stream_graph.reset();      // (the captured steps hold the other form's launches and buffers)
+    return prev;
+}
+int mg_set_beam_cross_absorb(mg_model* m, int absorb, int key_splits) {
+    if (!m) return fail(MG_E_ARG, "mg_set_beam_cross_absorb: null model");
+    if (key_splits < 0 || key_splits > 4) return fail(MG_E_ARG, "mg_set_beam_cross_absorb: key_splits must be in [0, 4] (0 = keep)");
+    std::lock_guard<std::recursive_mutex> lk(m->call_mu);
+    const int prev = m->beam_absorb;
+    if (absorb < 0) return prev;                        // query
+    if (absorb > 1) return fail(MG_E_ARG, "mg_set_beam_cross_absorb: absorb must be 0 (K / V form), 1 (absorbed) or < 0 (query)");
+    if (absorb && !xattn_supported(m->d, m->H)) return fail(MG_E_UNSUPPORTED, "mg_set_beam_cross_absorb: d_model %d / %d heads have no absorbed form", m->d, m->H);
+    m->beam_absorb = absorb;
+    if (key_splits) m->xb_split = key_splits;
     m->step_graph.reset(); m->stream_graph.reset();      // (the captured steps hold the other form's launches and buffers)
     return prev;
 }

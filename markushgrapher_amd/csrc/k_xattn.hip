@@ -78,6 +78,8 @@ MG_DEV void xa_wait_copies(int later) {        // at most `later` stages' copies
     else { if constexpr (KS == 1) MG_WAIT_VMCNT(3); else if constexpr (KS == 2) MG_WAIT_VMCNT(6); else if constexpr (KS == 4) MG_WAIT_VMCNT(12); else if constexpr (KS == 6) MG_WAIT_VMCNT(18); else MG_WAIT_VMCNT(24); }
 }
 
+// (xattn_beams_kernel below reproduces this kernel's bits per row.  It depends on which sums the device compiler contracts here - see the
+//  note above xa_fma; a change of those contractions shows up as a failure of tests/test_beam_cross_absorb.py on the device.)
 template <int NF, int NW, int NG>
 __global__ __launch_bounds__(NW * NG * 64) void xattn_stream_kernel(XAttnArgs a) {
     MG_DYN_SMEM(smem);
@@ -293,6 +295,276 @@ __global__ __launch_bounds__(NW * NG * 64) void xattn_stream_kernel(XAttnArgs a)
     }
 }
 
+// ---- the stream of beam search: the beams of an image share each stage --------------------------------------------------------
+// The `group` rows of an image (its beams) attend the same states.  One workgroup = (image, subset of BP of its beams, key split): a
+// stage is copied to LDS once and every wave feeds it to the score and context products of BP beams (B operands q'^T and P^T of the
+// beam, A operand shared).  Per beam, everything xattn_stream_kernel does for a row, in its order: the same feature partition over the
+// waves, the score partials summed through LDS in wave order (one slot per beam), the online-softmax state and the XA_DEFER rescale
+// decision of the beam, the same group merge order.  A row's bits are those xattn_stream_kernel writes at the same nsplit / nstg, and
+// do not depend on its sibling beams.  Register state per beam and wave: KS q'^T fragments + NF accumulators (d = 1024: 96 VGPRs).
+// Placement (speed only): the workgroups of an image (subsets x splits) take blocks of one residue mod 8 - on the observed round-robin
+// dispatch, one XCD - so that the later readers of a stage can find it in that XCD's L2 (measured, d 1024, 32 images x 5 beams: the launch
+// fetches 0.54-0.74 x the states' bytes from memory, the per-row kernel 2.1-2.6 x; profiles/r07_beam_cross_absorb.txt).  Block b: image 8 (b / 8 / per) + b % 8, work item
+// (b / 8) % per = split * subsets + subset.  Dead rows (live == 0) write nothing; a workgroup without a live row returns.
+// Rounding: the device compiler contracts three sums of xattn_stream_kernel into fused multiply-adds and nothing else - the RMSNorm
+// argument t * inv_d + eps, and in the group merge l * f0 + l' * f1 (l' * f1 rounded first) and acc * f0 + v * f1 (v * f1 rounded first
+// up to 8 f-tiles per wave, acc * f0 rounded first from 12 on: read from its gfx950 code).  This kernel turns contraction off and writes
+// those three as xa_fma in the same forms, so that its rows get the same bits (the emulator's build contracts nothing; the kernel tests
+// compare the two kernels bit for bit on the device).
+MG_DEV float xa_fma(float a, float b, float c) {
+#ifdef MG_EMU
+    return a * b + c;
+#else
+    return __builtin_fmaf(a, b, c);
+#endif
+}
+template <int NF, int NW, int NG, int BP>
+__global__ __launch_bounds__(NW * NG * 64) void xattn_beams_kernel(XAttnArgs a) {
+#pragma clang fp contract(off)
+    MG_DYN_SMEM(smem);
+    constexpr int KS = NF / 2;
+    const int tid = threadIdx.x, lane = tid & 63;
+#ifdef MG_EMU
+    const int w = tid >> 6;
+#else
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+#endif
+    const int gi = w / NW, wq = w - gi * NW;
+    const int G = a.group, nsub = (G + BP - 1) / BP, per = nsub * a.nsplit, nimg = a.rows / G;
+    const int x8 = blockIdx.x & 7, q8 = blockIdx.x >> 3, bunch = q8 / per, j = q8 - bunch * per;
+    const int img = bunch * 8 + x8;
+    if (img >= nimg) return;
+    const int split = j / nsub, sub = j - split * nsub;
+    const int row0 = img * G + sub * BP;
+    bool act[BP];                                    // beam present in the subset and live (uniform over the workgroup)
+    int rowb[BP];
+    bool any = false;
+#pragma unroll
+    for (int b = 0; b < BP; ++b) {
+        const bool in = sub * BP + b < G;
+        act[b] = in && !(a.live && a.live[row0 + b] == 0);
+        rowb[b] = in ? row0 + b : row0;
+        any = any || act[b];
+    }
+    if (!any) return;
+    const int owner = a.kv_owner ? a.kv_owner[img] : img;
+    const int nkeys = a.len[owner];
+    const int d = a.d, H = a.H, nch = d >> 3;
+    const int head = lane & 15, g = lane >> 4;
+    const int fb = wq * 16 * NF;
+    const int stage_bytes = XA_KEYS * d * 2;
+    const int R = a.nstg / NG;
+    char* ring = smem;
+    float* red = (float*)(smem + (size_t)R * NG * stage_bytes) + (size_t)gi * BP * NW * 256;     // [group][beam][NW][64][4]
+    const int nst_all = (nkeys + XA_KEYS - 1) / XA_KEYS;
+    const int per_split = (nst_all + a.nsplit - 1) / a.nsplit;
+    const int st0 = split * per_split, st1 = (st0 + per_split < nst_all) ? st0 + per_split : nst_all;
+    const int nst = st1 > st0 ? st1 - st0 : 0;
+    const int nit = (nst + NG - 1) / NG;
+    const int nst_g = nst > gi ? (nst - gi + NG - 1) / NG : 0;
+
+    mg_raw16 qr[BP][KS];
+#pragma unroll
+    for (int b = 0; b < BP; ++b) {
+        const uint16_t* qp = a.qx + ((size_t)rowb[b] * H + (head < H ? head : 0)) * d + fb + 8 * g;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) gld16_async(qr[b][ks], qp + ks * 32);
+    }
+    float qs2[BP];
+#pragma unroll
+    for (int b = 0; b < BP; ++b) {
+        float qs = 1.0f;
+        if (a.qrs.part) {
+            float t = 0.f;
+            for (int i = lane; i < a.qrs.nparts; i += 64) t += a.qrs.part[(size_t)rowb[b] * a.qrs.nparts + i];
+            t = sum_slots(sum8(t), lane);
+            qs = rsqrtf(xa_fma(t, a.qrs.inv_d, a.qrs.eps));
+        }
+        qs2[b] = qs * 1.44269504088896341f;
+    }
+    const char* ebase = (const char*)(a.enc + (size_t)owner * a.cap * d);
+    const int swz_mask = (nch < 16 ? nch : 16) - 1;
+    unsigned coff[KS];
+#pragma unroll
+    for (int c = 0; c < KS; ++c) {
+        const int inst = wq * KS + c, s = inst * 64 + lane;
+        const int key = s / nch, jj = s - key * nch;
+        coff[c] = (unsigned)(key * d * 2 + ((jj ^ (xa_swz(key) & swz_mask)) << 4));
+    }
+    const mg_lds_t ring_lds = mg_lds_addr(ring);
+    auto issue = [&](int it, int slot_it) {
+        const mg_lds_t dst = ring_lds + (unsigned)((slot_it * NG + gi) * stage_bytes + wq * KS * 1024);
+        const char* src = ebase + (size_t)(st0 + it * NG + gi) * (size_t)stage_bytes;
+        if (a.nt) { for (int c = 0; c < KS; ++c) glds16_async_sv_nt(src, coff[c], dst + c * 1024); }
+        else { for (int c = 0; c < KS; ++c) glds16_async_sv(src, coff[c], dst + c * 1024); }
+    };
+    constexpr int NSA = KS < 4 ? KS : 4, NTA = NF < 8 ? NF : 8;
+    unsigned sa[NSA], ta[NTA];
+    {
+        const int sx = xa_swz(head) & swz_mask;
+#pragma unroll
+        for (int k = 0; k < NSA; ++k) sa[k] = (unsigned)(head * d * 2 + ((((fb >> 3) + g + 4 * k) ^ sx) << 4));
+        const int ra = (lane & 15) >> 2, rb = lane & 3, tkey = 4 * g + ra, tx = xa_swz(tkey) & swz_mask;
+#pragma unroll
+        for (int k = 0; k < NTA; ++k) ta[k] = (unsigned)(tkey * d * 2 + ((((fb >> 3) + 4 * (k >> 1) + rb) ^ tx) << 4) + (k & 1) * 8);
+    }
+
+    f32x4 acc[BP][NF];
+    float mrun[BP], lsum[BP];
+#pragma unroll
+    for (int b = 0; b < BP; ++b) {
+#pragma unroll
+        for (int t = 0; t < NF; ++t) acc[b][t] = acc4_zero();
+        mrun[b] = XA_NEG; lsum[b] = 0.f;
+    }
+
+    MG_WAIT_VMCNT(0);
+    uint4 qf[BP][KS];
+#pragma unroll
+    for (int b = 0; b < BP; ++b)
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            MG_TIE(qr[b][ks]);
+            qf[b][ks] = head < H ? raw16_get(qr[b][ks]) : make_uint4(0, 0, 0, 0);
+        }
+    {
+        const int lead = R - 1;
+        for (int it = 0; it < lead && it < nst_g; ++it) issue(it, it);
+        int slot = 0, slot_lead = lead % R;
+        for (int it = 0; it < nit; ++it) {
+            {
+                int later = nst_g - 1 - it;
+                later = later < lead - 1 ? later : lead - 1;
+                xa_wait_copies<KS>(later);
+            }
+            MG_BARRIER_RAW();
+            const bool mine = it < nst_g;
+            if (it + lead < nst_g) issue(it + lead, slot_lead);
+            const char* stg = ring + (size_t)(slot * NG + gi) * stage_bytes;
+            slot = slot + 1 == R ? 0 : slot + 1;
+            slot_lead = slot_lead + 1 == R ? 0 : slot_lead + 1;
+            if (mine) {          // score partials of every beam: one LDS read of the stage operand feeds BP products
+                f32x4 s0[BP], s1[BP];
+#pragma unroll
+                for (int b = 0; b < BP; ++b) { s0[b] = acc4_zero(); s1[b] = acc4_zero(); }
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) {
+                    const uint4 e = ld16(stg + sa[ks & 3] + (ks >> 2) * 256);
+#pragma unroll
+                    for (int b = 0; b < BP; ++b)
+                        if (act[b]) { if (ks & 1) s1[b] = mfma16(e, qf[b][ks], s1[b]); else s0[b] = mfma16(e, qf[b][ks], s0[b]); }
+                }
+#pragma unroll
+                for (int b = 0; b < BP; ++b)
+                    if (act[b]) ((float4*)red)[((size_t)b * NW + wq) * 64 + lane] =
+                                    make_float4(s0[b][0] + s1[b][0], s0[b][1] + s1[b][1], s0[b][2] + s1[b][2], s0[b][3] + s1[b][3]);
+            }
+            MG_WAIT_LGKM0();
+            MG_BARRIER_RAW();
+            if (!mine) continue;
+            const int sti = st0 + it * NG + gi;
+            uint2 pt[BP];
+#pragma unroll
+            for (int b = 0; b < BP; ++b) {
+                pt[b] = make_uint2(0, 0);
+                if (!act[b]) continue;
+                float sc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ww = 0; ww < NW; ++ww) {
+                    const float4 v = ((const float4*)red)[((size_t)b * NW + ww) * 64 + lane];
+                    sc[0] += v.x; sc[1] += v.y; sc[2] += v.z; sc[3] += v.w;
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sc[e] *= qs2[b];
+                if (sti + 1 == nst_all) {
+                    const int kbase = sti * XA_KEYS + 4 * g;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) sc[e] = (kbase + e < nkeys) ? sc[e] : XA_NEG;
+                }
+                float mx = fmaxf(fmaxf(sc[0], sc[1]), fmaxf(sc[2], sc[3]));
+                mx = fmaxf(mx, lane_xor<16>(mx, lane));
+                mx = fmaxf(mx, lane_xor<32>(mx, lane));
+                if (wave_any(mx > mrun[b] + XA_DEFER)) {
+                    const float mn = fmaxf(mrun[b], mx);
+                    const float al = fast_exp2(mrun[b] - mn);
+                    mrun[b] = mn;
+                    lsum[b] *= al;
+#pragma unroll
+                    for (int t = 0; t < NF; ++t) {
+                        acc[b][t][0] *= al; acc[b][t][1] *= al; acc[b][t][2] *= al; acc[b][t][3] *= al;
+                    }
+                }
+                pt[b] = make_uint2(pack_bf16(fast_exp2(sc[0] - mrun[b]), fast_exp2(sc[1] - mrun[b])),
+                                   pack_bf16(fast_exp2(sc[2] - mrun[b]), fast_exp2(sc[3] - mrun[b])));
+                lsum[b] += (bf16lo(pt[b].x) + bf16hi(pt[b].x)) + (bf16lo(pt[b].y) + bf16hi(pt[b].y));
+            }
+#pragma unroll
+            for (int t = 0; t < NF; ++t) {           // context: one transposed read of the stage feeds BP products
+                const uint2 e = lds_read_tr16(stg + ta[t & 7] + (t >> 3) * 256);
+#pragma unroll
+                for (int b = 0; b < BP; ++b)
+                    if (act[b]) acc[b][t] = mfma16k16(e, pt[b], acc[b][t]);
+            }
+        }
+    }
+    // wave groups merged in group order, one beam at a time through the ring's memory (as xattn_stream_kernel)
+    if constexpr (NG > 1) {
+        float4* mb = (float4*)smem;
+        float2* mm = (float2*)(smem + (size_t)NW * NF * 64 * 16);
+#pragma unroll
+        for (int b = 0; b < BP; ++b) {
+            if (!act[b]) continue;
+            for (int gsrc = 1; gsrc < NG; ++gsrc) {
+                MG_WAIT_LGKM0();
+                MG_BARRIER_RAW();
+                if (gi == gsrc) {
+#pragma unroll
+                    for (int t = 0; t < NF; ++t) mb[((size_t)wq * NF + t) * 64 + lane] = make_float4(acc[b][t][0], acc[b][t][1], acc[b][t][2], acc[b][t][3]);
+                    mm[(size_t)wq * 64 + lane] = make_float2(mrun[b], lsum[b]);
+                }
+                MG_WAIT_LGKM0();
+                MG_BARRIER_RAW();
+                if (gi == 0) {
+                    const float2 o = mm[(size_t)wq * 64 + lane];
+                    const float M = fmaxf(mrun[b], o.x);
+                    const float f0 = fast_exp2(mrun[b] - M), f1 = fast_exp2(o.x - M);
+                    mrun[b] = M;
+                    lsum[b] = xa_fma(lsum[b], f0, o.y * f1);
+#pragma unroll
+                    for (int t = 0; t < NF; ++t) {
+                        const float4 v = mb[((size_t)wq * NF + t) * 64 + lane];
+                        if constexpr (NF >= 12) {
+                            acc[b][t][0] = xa_fma(v.x, f1, acc[b][t][0] * f0); acc[b][t][1] = xa_fma(v.y, f1, acc[b][t][1] * f0);
+                            acc[b][t][2] = xa_fma(v.z, f1, acc[b][t][2] * f0); acc[b][t][3] = xa_fma(v.w, f1, acc[b][t][3] * f0);
+                        } else {
+                            acc[b][t][0] = xa_fma(acc[b][t][0], f0, v.x * f1); acc[b][t][1] = xa_fma(acc[b][t][1], f0, v.y * f1);
+                            acc[b][t][2] = xa_fma(acc[b][t][2], f0, v.z * f1); acc[b][t][3] = xa_fma(acc[b][t][3], f0, v.w * f1);
+                        }
+                    }
+                }
+            }
+        }
+        if (gi != 0) return;
+    }
+#pragma unroll
+    for (int b = 0; b < BP; ++b) {
+        if (!act[b]) continue;
+        float l = lsum[b];
+        l += lane_xor<16>(l, lane);
+        l += lane_xor<32>(l, lane);
+        if (head < H) {
+            const size_t pi = ((size_t)rowb[b] * a.nsplit + split) * H + head;
+            const float inv = l > 0.f ? 1.0f / l : 0.f;
+            uint16_t* pp = a.part + pi * d + fb + 8 * g;
+#pragma unroll
+            for (int p2 = 0; p2 < NF / 2; ++p2)
+                st16(pp + 32 * p2, make_uint4(pack_bf16(acc[b][2 * p2][0] * inv, acc[b][2 * p2][1] * inv), pack_bf16(acc[b][2 * p2][2] * inv, acc[b][2 * p2][3] * inv),
+                                              pack_bf16(acc[b][2 * p2 + 1][0] * inv, acc[b][2 * p2 + 1][1] * inv), pack_bf16(acc[b][2 * p2 + 1][2] * inv, acc[b][2 * p2 + 1][3] * inv)));
+            if (wq == 0 && g == 0) { a.ml[pi * 2] = mrun[b]; a.ml[pi * 2 + 1] = l; }
+        }
+    }
+}
+
 // ---- ctx_h = (merged c_h / l) · Wv_h^T ------------------------------------------------------------------------------------
 // grid (H, ceil(rows / 16)), 4 waves splitting the d features (k-steps w, w + 4, ...), partial tiles summed through LDS in wave order.
 // wv: fragment order [H][d/32 k-steps][4 tiles][64 lanes][8]: lane (m, g) of tile tl holds Wv[h*64 + j(m, tl)][32 ks + 8 g .. + 8],
@@ -467,6 +739,47 @@ void xattn_stream_prepare(int d, int nstg) {
 #define MG_XP(N, W) if (nf == N && nw == W) { if (ng == 2) MG_SET_MAX_SMEM((&xattn_stream_kernel<N, W, 2>), sh); else MG_SET_MAX_SMEM((&xattn_stream_kernel<N, W, 1>), sh); return; }
     MG_XP(2, 2) MG_XP(2, 4) MG_XP(4, 4) MG_XP(8, 4) MG_XP(12, 4) MG_XP(16, 4)
 #undef MG_XP
+}
+
+// Beams per workgroup of the beam-search stream.  Two wave groups (nstg = 4, two waves per SIMD: at most 256 registers per wave) hold the
+// state of two beams; one wave group (nstg = 3, one wave per SIMD) that of two or three - three only up to 12 f-tiles per wave (d = 1024,
+// 16 f-tiles: three beams' fragments and accumulators spill even at 512 registers).  Returns 0 where the form is not supported.
+int xattn_beams_bp(int d, int nstg, int bp) {
+    if (bp == 0) return 2;
+    if (bp == 2 || (bp == 3 && nstg == 3 && xattn_nf(d) <= 12)) return bp;
+    return 0;
+}
+size_t xattn_beams_lds(int d, int nstg, int bp) {
+    const int nf = xattn_nf(d), nw = nf ? d / (16 * nf) : 1;
+    return (size_t)nstg * XA_KEYS * d * 2 + (size_t)xa_groups(nstg) * bp * nw * 64 * 16;       // ring + score partials of every beam
+}
+template <int N, int W>
+static void xa_beams_launch(const XAttnArgs& a, int ng, int bp, mgStream_t stream) {
+    const int nimg = a.rows / a.group, nsub = (a.group + bp - 1) / bp;
+    const dim3 grid((unsigned)(((nimg + 7) / 8) * 8 * nsub * a.nsplit)), block(W * ng * 64);      // images rounded up to 8 (placement)
+    const size_t sh = xattn_beams_lds(a.d, a.nstg, bp);
+    if (ng == 2) MG_LAUNCH((xattn_beams_kernel<N, W, 2, 2>), grid, block, sh, stream, a);
+    else if (bp == 2) MG_LAUNCH((xattn_beams_kernel<N, W, 1, 2>), grid, block, sh, stream, a);
+    else if constexpr (N <= 12) MG_LAUNCH((xattn_beams_kernel<N, W, 1, 3>), grid, block, sh, stream, a);
+}
+template <int N, int W>
+static void xa_beams_prepare(int d) {
+    MG_SET_MAX_SMEM((&xattn_beams_kernel<N, W, 2, 2>), xattn_beams_lds(d, 4, 2));
+    MG_SET_MAX_SMEM((&xattn_beams_kernel<N, W, 1, 2>), xattn_beams_lds(d, 3, 2));
+    if constexpr (N <= 12) MG_SET_MAX_SMEM((&xattn_beams_kernel<N, W, 1, 3>), xattn_beams_lds(d, 3, 3));
+    (void)d;
+}
+void xattn_stream_beams(const XAttnArgs& a, mgStream_t stream) {
+    const int nf = xattn_nf(a.d), nw = a.d / (16 * nf), ng = xa_groups(a.nstg), bp = xattn_beams_bp(a.d, a.nstg, a.bpw);
+#define MG_XB(N, W) if (nf == N && nw == W) return xa_beams_launch<N, W>(a, ng, bp, stream);
+    MG_XB(2, 2) MG_XB(2, 4) MG_XB(4, 4) MG_XB(8, 4) MG_XB(12, 4) MG_XB(16, 4)
+#undef MG_XB
+}
+void xattn_beams_prepare(int d) {
+    const int nf = xattn_nf(d), nw = nf ? d / (16 * nf) : 0;
+#define MG_XB(N, W) if (nf == N && nw == W) return xa_beams_prepare<N, W>(d);
+    MG_XB(2, 2) MG_XB(2, 4) MG_XB(4, 4) MG_XB(8, 4) MG_XB(12, 4) MG_XB(16, 4)
+#undef MG_XB
 }
 
 void xattn_contract(const XAttnArgs& a, mgStream_t stream) {

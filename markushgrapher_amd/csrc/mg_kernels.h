@@ -336,6 +336,8 @@ struct XAttnArgs {
     int nsplit;               // key splits per row (1 .. 4): workgroups of the stream = rows * nsplit
     int nstg;                 // stages of 16 keys in the stream's LDS ring: 4 = two wave groups (136 KB), 3 = one wave group (100 KB)
     int nt;                   // 1: the stream's copies carry the non-temporal hint
+    int group;                // beam-search stream (xattn_stream_beams): rows per K / V owner; owner of row r = kv_owner ? kv_owner[r / group] : r / group
+    int bpw;                  // beam-search stream: beams per workgroup (0 = xattn_beams_bp's choice)
 };
 bool xattn_supported(int d, int H);
 int xattn_nf(int d);
@@ -344,6 +346,12 @@ void xattn_stream_prepare(int d, int nstg);    // once per width, outside any st
 void xattn_expand(const XAttnArgs& a, mgStream_t stream);
 void xattn_stream(const XAttnArgs& a, mgStream_t stream);
 void xattn_contract(const XAttnArgs& a, mgStream_t stream);
+// beam search (group > 1 rows per owner, rows a multiple of group): the same bits per row as xattn_stream at the same nsplit / nstg,
+// one workgroup per (image, subset of beams, key split); kv_owner (nullable) is indexed by image
+int xattn_beams_bp(int d, int nstg, int bp);   // beams per workgroup for a width and a ring of nstg stages (bp = 0: the default), 0 = not supported
+size_t xattn_beams_lds(int d, int nstg, int bp);
+void xattn_beams_prepare(int d);               // as xattn_stream_prepare, every form of the width
+void xattn_stream_beams(const XAttnArgs& a, mgStream_t stream);
 void xattn_pack_weights(const float* wkv_f32, uint16_t* wk, uint16_t* wv, int H, int d, mgStream_t stream);
 // rows of a packed [rows][d] bf16 operand -> natural rows dst[b][row_map[r]][d] (row_map < 0: dropped)
 void enc_rows(const uint16_t* src_pk, const int* row_map, uint16_t* dst, int B, int rows_per_image, int cap, int d, mgStream_t stream);

@@ -124,6 +124,7 @@ class Engine:
         L.mg_attach_e1.argtypes = [C.c_void_p, C.c_void_p]
         L.mg_set_shared_gpu.argtypes = [C.c_void_p, C.c_int]
         L.mg_set_cross_absorb.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.mg_set_beam_cross_absorb.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.mg_decode_graph_active.argtypes = [C.c_void_p]
         L.mg_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         L.mg_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -175,6 +176,21 @@ class Engine:
         """False / True / "auto": the cross-attention form greedy calls of this context run (mg_set_cross_absorb)."""
         prev = int(self.lib.mg_set_cross_absorb(self.model, -1, 0))
         return "auto" if prev == 2 else bool(prev)
+
+    def set_beam_cross_absorb(self, on: bool, key_splits: int = 0) -> bool:
+        """Beam-search cross-attention form (include/mgrapher.h mg_set_beam_cross_absorb), independent of set_cross_absorb: True = weight-
+        absorbed (one workgroup serves several beams of an image, every stage of its states read once for all of them), False (default) =
+        per-layer K / V streams.  key_splits 1..4 (0 keeps the setting).  Covers generate(num_beams > 1) and generate_stream_beam; clones
+        made afterwards inherit it.  The workspaces are re-sized at the next call.  Returns the previous setting."""
+        prev = self._chk(self.lib.mg_set_beam_cross_absorb(self.model, 1 if on else 0, int(key_splits)))
+        self._ws, self._ws_bytes = None, 0
+        self._sws, self._sws_bytes = None, 0
+        return bool(prev)
+
+    @property
+    def beam_cross_absorb(self) -> bool:
+        """True if beam-search calls of this context run the weight-absorbed cross-attention (mg_set_beam_cross_absorb)."""
+        return bool(self._chk(self.lib.mg_set_beam_cross_absorb(self.model, -1, 0)))
 
     ABSORB_AUTO_ROWS = 96      # "auto": calls with at least this many decode rows take the absorbed form (engine.hip MG_ABSORB_AUTO_ROWS)
 

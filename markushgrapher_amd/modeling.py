@@ -125,6 +125,7 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
         self._weight_dtype = weight_dtype
         self._engine: Optional[Engine] = None
         self._engine_device = None
+        self._beam_absorb = (False, 0)      # set_beam_cross_absorb: (on, key splits), applied to every engine / context this model makes
         self._tree = _ParamTree()
         for key, shp, _ in state_dict_spec(self._shape):
             self._tree.add(key, torch.zeros(shp, dtype=weight_dtype))
@@ -340,8 +341,24 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
                         f"scale {tuple(shape1.pix_scale)} / shift {tuple(shape1.pix_shift)} (MolScribe itself trains on ImageNet mean/std: set "
                         "config.e1 = dict(markushgrapher_amd.e1_shapes.IMAGENET_RENORM) if your checkpoint expects that), projector activation "
                         f"'{shape1.proj_act}', decoder keys = [e1 | VTL states].  Pass e1= to supply the tokens yourself.", stacklevel=2)
+            if self._beam_absorb[0]:
+                eng.set_beam_cross_absorb(*self._beam_absorb)
             self._engine, self._engine_device = eng, dev
         return self._engine
+
+    def set_beam_cross_absorb(self, on: bool, key_splits: int = 0) -> bool:
+        """Beam search (generate(num_beams > 1), generate_queue(num_beams > 1)) with the weight-absorbed cross-attention (Engine.
+        set_beam_cross_absorb; default off: the K / V form).  Contexts made afterwards by in_flight() and generate_queue(contexts=...) inherit
+        it, as do the ones generate_queue keeps.  Not part of the saved config.  Returns the previous setting."""
+        eng = self._eng()
+        prev = eng.set_beam_cross_absorb(on, key_splits)
+        self._beam_absorb = (bool(on), int(key_splits))
+        fl = getattr(self, "_inflight", None)
+        if fl is not None:
+            for c in fl.contexts:
+                if c is not eng:
+                    c.set_beam_cross_absorb(on, key_splits)
+        return prev
 
     def _shift_right(self, labels):                          # stock:791-811
         out = labels.new_zeros(labels.shape)
