@@ -112,6 +112,33 @@ int mg_generate(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int6
                 int min_length, float length_penalty, int early_stopping, int64_t* out_ids, int* out_cols_host,
                 float* out_scores, float* step_top2);
 
+/* Scored generation: confidence scores and the n-best list of beam search, computed on the device beside the ids.  Every pointer is
+ * nullable (device memory); a NULL opts is the unscored call.  rows_out = B * num_return (queue forms: N * num_return), hypotheses of an
+ * image consecutive, best first.
+ *   num_return    hypotheses per image, in [1, num_beams] (greedy: 1; stock num_return_sequences)
+ *   token_scores  [rows_out][max_length-1] f32: column j scores the token in column j+1 of the ids.
+ *                 greedy: log_softmax of the step's processed logits at the emitted token - stock compute_transition_scores(sequences,
+ *                 scores, normalize_logits=True) for every token up to and including the row's EOS.  MinLength-suppressed stop tokens
+ *                 are not part of the normaliser, as in stock's processed scores.  Columns after a row's EOS hold 0.0 (stock scores the
+ *                 pad token there).
+ *                 beam: the processed log-probability of each token of the hypothesis (without the running score) - stock
+ *                 compute_transition_scores(sequences, scores, beam_indices, normalize_logits=False); 0.0 past the hypothesis' length.
+ *   seq_scores    [rows_out] f32, beam only: sequences_scores (the length-penalised score).  Replaces out_scores of the unscored call.
+ *   beam_indices  [rows_out][max_length-1] i32, beam only: stock beam_indices (flat row image * num_beams + beam each token was chosen
+ *                 from; -1 past the hypothesis' length).
+ * Beam: out_ids holds rows_out rows; *out_cols_host (queue: out_len[image]) = the longest returned hypothesis' columns.
+ * The scores cost little (the greedy lm_head epilogue adds one exp per logit; the beam state keeps one more float history). */
+typedef struct mg_gen_opts {
+    int num_return;
+    float* token_scores;
+    float* seq_scores;
+    int32_t* beam_indices;
+} mg_gen_opts;
+int mg_generate_scored(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
+                       const uint8_t* attention_mask, const float* pixel_values, const float* e1, int M_e1, int B, int L, int num_beams,
+                       int max_length, int min_length, float length_penalty, int early_stopping, int64_t* out_ids, int* out_cols_host,
+                       float* out_scores, float* step_top2, const mg_gen_opts* opts);
+
 /* Limits: B * num_beams <= 256 live sequences per call (MG_E_UNSUPPORTED beyond; split the batch), num_beams <= 8. */
 
 /* Continuous greedy decoding of N images - what the reference's evaluation loop does one image at a time with
@@ -140,6 +167,15 @@ int mg_generate_stream_beam(mg_model* m, void* stream, void* ws, size_t ws_bytes
                             const uint8_t* attention_mask, const float* pixel_values, int N, int L, int chunk, int slots, int pool_chunks,
                             int num_beams, int max_length, int min_length, float length_penalty, int early_stopping, int64_t* out_ids,
                             int32_t* out_len, float* out_scores, long* steps_host);
+/* The queue forms with the outputs of mg_gen_opts (see mg_generate_scored): token_scores / seq_scores / beam_indices per image
+ * (rows_out = N * num_return; beam: out_ids [N * num_return][max_length], out_len [N] = the longest returned hypothesis' columns). */
+int mg_generate_stream_scored(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
+                              const uint8_t* attention_mask, const float* pixel_values, int N, int L, int chunk, int slots, int pool_chunks,
+                              int max_length, int min_length, int64_t* out_ids, int32_t* out_len, long* steps_host, const mg_gen_opts* opts);
+int mg_generate_stream_beam_scored(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
+                                   const uint8_t* attention_mask, const float* pixel_values, int N, int L, int chunk, int slots, int pool_chunks,
+                                   int num_beams, int max_length, int min_length, float length_penalty, int early_stopping, int64_t* out_ids,
+                                   int32_t* out_len, long* steps_host, const mg_gen_opts* opts);
 /* Where the encoder of mg_generate_stream runs: 0 = on the caller's stream (serial), 1 = own stream at the lowest priority
  * (default), 2 = own stream restricted to the compute units of cu_mask (nwords x 32 bits, hipExtStreamCreateWithCUMask). */
 int mg_stream_encoder_mode(mg_model* m, int mode, const uint32_t* cu_mask, int nwords);

@@ -217,6 +217,47 @@ int mgk_greedy_select(void* stream, const float* logits, int rows, int V, int ld
     return MG_OK;
 }
 
+// greedy_select with token scores (ArgmaxArgs::token_scores [rows][ts_ld], written at column pos - 1)
+int mgk_greedy_select_scored(void* stream, const float* logits, int rows, int V, int ldl, int eos, int pad, int min_len,
+                             int64_t* next_ids, int64_t* out_ids, int max_len, int pos, int* unfinished, int* n_unfinished,
+                             float* token_scores, int ts_ld) {
+    ArgmaxArgs a{};
+    a.logits = logits; a.rows = rows; a.V = V; a.ldl = ldl; a.eos = eos; a.pad = pad; a.min_len = min_len;
+    a.next_ids = next_ids; a.out_ids = out_ids; a.max_len = max_len; a.pos = pos; a.unfinished = unfinished;
+    a.n_unfinished = n_unfinished; a.token_scores = token_scores; a.ts_ld = ts_ld;
+    mg_memset_async(n_unfinished, 0, sizeof(int), (mgStream_t)stream);
+    greedy_select(a, (mgStream_t)stream);
+    return MG_OK;
+}
+
+// The lm_head form of the fused greedy tail (gemm_rows_splitk with TopOut, KS = 1): P [M][ldp] logits (nullable: not written),
+// ptop [M][ceil(N/32)] float4 partials, stopv [M][4]; stop token `eos` kept apart; lse = TopOut::lse
+int mgk_lm_head_top(void* stream, const void* X_pk, const void* W_pk, float* P, int M, int N, int K, int ldp, void* ptop, float* stopv,
+                    int eos, int lse) {
+    if ((K & 63) || M > 256 || M < 1) return MG_E_SHAPE;
+    RowScale rs{};
+    TopOut top{(float4*)ptop, stopv, {eos, -1, -1, -1}, P ? 1 : 0, lse ? 1 : 0};
+    gemm_rows_splitk((const uint16_t*)X_pk, (const uint16_t*)W_pk, P, M, N, K, ldp, 0, 1, rs, (mgStream_t)stream, &top);
+    return MG_OK;
+}
+
+// greedy_select_fused on lm_head partials (mgk_lm_head_top): selection, bookkeeping, optional token scores, and the next step's embedding
+// + first RMSNorm of the selected token (tok_emb [V][d] bf16, gain [d], h [rows][d] fp32, x_pk packed bf16 [rows padded to 32][d])
+int mgk_greedy_select_fused(void* stream, const void* ptop, const float* stopv, int rows, int V, int eos, int pad, int min_len,
+                            int64_t* next_ids, int64_t* out_ids, int max_len, int pos, int* unfinished, int* n_unfinished, float* token_scores,
+                            int ts_ld, const void* tok_emb, const float* gain, float* h, void* x_pk, int d, float eps) {
+    if (d > 2048 || (d & 7)) return MG_E_SHAPE;
+    ArgmaxArgs a{};
+    a.rows = rows; a.V = V; a.ldl = (V + 31) / 32 * 32; a.eos = eos; a.pad = pad; a.min_len = min_len;
+    a.next_ids = next_ids; a.out_ids = out_ids; a.max_len = max_len; a.pos = pos; a.unfinished = unfinished;
+    a.n_unfinished = n_unfinished; a.token_scores = token_scores; a.ts_ld = ts_ld;
+    a.ptop = (const float4*)ptop; a.stopv = stopv; a.ntiles = (V + 31) / 32;
+    a.tok_emb = (const uint16_t*)tok_emb; a.gain = gain; a.h = h; a.x_pk = (uint16_t*)x_pk; a.d = d; a.eps = eps;
+    mg_memset_async(n_unfinished, 0, sizeof(int), (mgStream_t)stream);
+    greedy_select_fused(a, (mgStream_t)stream);
+    return MG_OK;
+}
+
 int mgk_gemm_splitk(void* stream, const void* X_pk, const void* W_pk, float* P, int M, int N, int K, int ldp,
                     size_t slab_stride, int KS) {
     if ((K & 63) || KS < 1 || KS > 16 || M > 256) return MG_E_SHAPE;

@@ -57,10 +57,14 @@ struct StepGraph {
         int B, L, K, max_length, min_length, early_stopping, M_e1;
         float length_penalty;
         const void* scores;      // beam queue: beam_slot_end_kernel holds the out_scores pointer (NULL or a buffer) inside the captured launch
+        // scored calls (mg_gen_opts): the selection / slot-end launches hold the token-score and beam-index pointers and the n-best count
+        const void *token_scores, *beam_indices;
+        int num_return;
         bool operator==(const Key& o) const {
             return ws == o.ws && out_ids == o.out_ids && top2 == o.top2 && stream == o.stream && B == o.B && L == o.L && K == o.K && M_e1 == o.M_e1 &&
                    max_length == o.max_length && min_length == o.min_length && early_stopping == o.early_stopping &&
-                   length_penalty == o.length_penalty && scores == o.scores;
+                   length_penalty == o.length_penalty && scores == o.scores && token_scores == o.token_scores &&
+                   beam_indices == o.beam_indices && num_return == o.num_return;
         }
     };
     Key key{};
@@ -630,6 +634,9 @@ struct DecodeCtx {
     int *bpool, *assign;
     int32_t* out_len;
     float* out_scores;
+    // scored calls: greedy token log-probabilities [rows or images][max_length - 1] (nullable); beam queue: the n-best output
+    float* token_scores;
+    BeamOut nbest;
 };
 
 // Decode step, 6 launches per layer: QKV -> self-attention -> [O residual | cross-Q] -> cross-attention ->
@@ -748,7 +755,7 @@ static void decode_step(mg_model* m, const DecodeCtx& c, int t, const int* tdev,
         }
     }
     if (fused_tail) {          // lm_head with per-workgroup top-2 partials (no fp32 logits), stop token kept apart for MinLength
-        TopOut top{c.ptop, c.stopv, {m->c.eos_token_id, -1, -1, -1}, 0};
+        TopOut top{c.ptop, c.stopv, {m->c.eos_token_id, -1, -1, -1}, 0, c.token_scores != nullptr ? 1 : 0};
         if (!(whatif & 64)) gemm_rows_splitk(c.dx_pk, m->at<uint16_t>(m->lm_head), c.logits, R, m->V, d, ldl, 0, 1, rs0, st, &top);
     } else {
         gemm_rows_splitk(c.dx_pk, m->at<uint16_t>(m->lm_head), c.logits, R, m->V, d, ldl, 0, 1, rs0, st);
@@ -765,6 +772,7 @@ static void decode_step(mg_model* m, const DecodeCtx& c, int t, const int* tdev,
         g.top2 = step_top2 ? (tdev ? step_top2 : step_top2 + (size_t)(t + 1) * R * 2) : nullptr;
         g.step_ctr = stream ? nullptr : counters;      // the last workgroup to finish does the step bookkeeping (no step_end launch)
         g.slots = c.slots;
+        g.token_scores = c.token_scores; g.ts_ld = max_length - 1;
         if (fused_tail) {
             g.ptop = c.ptop; g.stopv = c.stopv; g.ntiles = ldl / 32;
             g.tok_emb = m->at<uint16_t>(m->tok_emb); g.h = c.dh; g.gain = m->at<float>(m->dec[0].ln0); g.x_pk = c.dx_pk;
@@ -784,7 +792,7 @@ static void decode_step(mg_model* m, const DecodeCtx& c, int t, const int* tdev,
         beam_reorder_anc(c.anc, c.beam_idx, R, max_length - 1, nullptr, counters, st, &bs);
         beam_slots_step(c.beam_state, B, K, max_length, (int)pad, m->c.eos_token_id, c.slots.start_id, early_stopping, c.slots.pos, c.slots.img,
                         c.slots.pool, c.bpool, c.unfinished, c.assign, c.next_ids, c.anc, T_cap, c.slots.pool_cap, out_ids, c.out_len,
-                        c.out_scores, c.slots.ctr, true, st);
+                        c.out_scores, c.slots.ctr, true, st, &c.nbest);
     } else {
         beam_step(c.beam_state, c.logits, ldl, m->V, B, K, max_length, t + 1, tdev, c.beam_div, m->c.eos_token_id, min_length,
                   length_penalty, early_stopping, c.next_ids, c.beam_idx, counters, st);
@@ -1321,9 +1329,22 @@ int mg_generate(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int6
                 const uint8_t* attention_mask, const float* pixel_values, const float* e1, int M_e1, int B, int L, int num_beams, int max_length,
                 int min_length, float length_penalty, int early_stopping, int64_t* out_ids, int* out_cols_host,
                 float* out_scores, float* step_top2) {
+    return mg_generate_scored(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, e1, M_e1, B, L, num_beams, max_length,
+                              min_length, length_penalty, early_stopping, out_ids, out_cols_host, out_scores, step_top2, nullptr);
+}
+
+int mg_generate_scored(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
+                       const uint8_t* attention_mask, const float* pixel_values, const float* e1, int M_e1, int B, int L, int num_beams,
+                       int max_length, int min_length, float length_penalty, int early_stopping, int64_t* out_ids, int* out_cols_host,
+                       float* out_scores, float* step_top2, const mg_gen_opts* opts) {
     entry_drain();
     if (!m || !out_ids || !out_cols_host) return fail(MG_E_ARG, "mg_generate: null argument");
     MG_ONE_CALL(m, "mg_generate");
+    const int num_return = opts ? opts->num_return : 1;
+    if (num_return < 1 || num_return > num_beams)
+        return fail(MG_E_ARG, "mg_generate: num_return (%d) must be in [1, num_beams = %d]", num_return, num_beams);
+    float* token_scores = opts ? opts->token_scores : nullptr;
+    int32_t* beam_indices = opts ? opts->beam_indices : nullptr;
     if (max_length < 2 || max_length > m->T_cap) return fail(MG_E_SHAPE, "mg_generate: max_length must be in [2, %d]", m->T_cap);
     if (num_beams < 1 || num_beams > 8) return fail(MG_E_UNSUPPORTED, "mg_generate: num_beams must be in [1, 8]");
     // the decode-step projections keep all live rows of a workgroup's feature slice in registers: at most 8 row tiles
@@ -1410,6 +1431,10 @@ int mg_generate(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int6
     dc.beam_state = w.beam_state; dc.counters = counters;
     dc.B = B; dc.K = K; dc.R = R; dc.max_length = max_length; dc.min_length = min_length; dc.early_stopping = early_stopping;
     dc.length_penalty = length_penalty; dc.out_ids = out_ids; dc.step_top2 = step_top2; dc.live = live;
+    if (K == 1 && token_scores) {      // columns a row does not reach (after its EOS, after the last step) hold 0
+        dc.token_scores = token_scores;
+        mg_memset_async(token_scores, 0, (size_t)B * (max_length - 1) * sizeof(float), st);
+    }
     // greedy batch calls run the fused tail (lm_head top-2 partials -> selection + next embedding in one launch); the parity
     // instrumentation needs the full logits / overrides the fed token, and d_model > 2048 would change the norm's summation order
     const bool fused_tail = K == 1 && m->fused_tail && !m->dbg_logits && !m->dbg_forced && d <= 2048;
@@ -1423,7 +1448,8 @@ int mg_generate(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int6
     const bool instrumented = m->dbg_logits || m->dbg_forced;      // by-value eager launches of the same kernels
 #ifndef MG_EMU
     if (m->use_graph == 1 && !instrumented) {
-        const StepGraph::Key key{ws, out_ids, step_top2, (const void*)st, B, L, K, max_length, min_length, early_stopping, M_e1, length_penalty, nullptr};
+        const StepGraph::Key key{ws, out_ids, step_top2, (const void*)st, B, L, K, max_length, min_length, early_stopping, M_e1, length_penalty, nullptr,
+                                 dc.token_scores, nullptr, 1};
         StepGraph& sg = m->step_graph;
         if (!(sg.valid && sg.key == key)) {
             std::lock_guard<std::mutex> capture_lock(mg_capture_mutex());
@@ -1483,7 +1509,10 @@ int mg_generate(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int6
             if (host_flag[0] == 0) break;
         }
     }
-    if (K > 1) beam_finalize(w.beam_state, B, K, max_length, out_ids, counters + 4, out_scores, st);
+    if (K > 1) {
+        const BeamOut nb{num_return, beam_indices, token_scores};
+        beam_finalize(w.beam_state, B, K, max_length, out_ids, counters + 4, opts ? opts->seq_scores : out_scores, st, &nb);
+    }
     if (m->phase_on) mg_event_record(m->phase_ev[2], st);
     std::vector<int> xlen_host;
     if (m->prof_used) { xlen_host.resize(B); mg_memcpy_async(xlen_host.data(), w.xlen, (size_t)B * sizeof(int), st); }
@@ -1551,7 +1580,7 @@ int mg_stream_encoder_mode(mg_model* m, int mode, const uint32_t* cu_mask, int n
 static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
                                 const uint8_t* attention_mask, const float* pixel_values, int N, int L, int chunk, int slots, int pool_chunks,
                                 int K, int max_length, int min_length, float length_penalty, int early_stopping, int64_t* out_ids,
-                                int32_t* out_len, float* out_scores, long* steps_host, const char* who) {
+                                int32_t* out_len, float* out_scores, long* steps_host, const char* who, const mg_gen_opts* opts) {
     entry_drain();
     if (!m || !ws || !input_ids || !bbox || !pixel_values || !out_ids || !out_len) return fail(MG_E_ARG, "%s: null argument", who);
     MG_ONE_CALL(m, "mg_generate_stream");
@@ -1562,6 +1591,10 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
     if (slots > pool_chunks * chunk) return fail(MG_E_SHAPE, "%s: slots (%d) exceed the %d pool entries", who, slots, pool_chunks * chunk);
     if (max_length < 2 || max_length > m->T_cap) return fail(MG_E_SHAPE, "%s: max_length must be in [2, %d]", who, m->T_cap);
     if (m->dbg_logits || m->dbg_forced) return fail(MG_E_STATE, "%s: the decode-capture instrumentation is for mg_generate", who);
+    const int num_return = opts ? opts->num_return : 1;
+    if (num_return < 1 || num_return > K) return fail(MG_E_ARG, "%s: num_return (%d) must be in [1, num_beams = %d]", who, num_return, K);
+    float* token_scores = opts ? opts->token_scores : nullptr;
+    if (opts && K > 1) out_scores = opts->seq_scores;
     const int R = slots * K;                         // decode rows
     StreamWs w;
     carve_stream(m, (char*)ws, chunk, L, slots, pool_chunks, &w, K, max_length);
@@ -1622,13 +1655,19 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
     dc.out_ids = out_ids; dc.live = w.unfinished;
     dc.anc = w.anc; dc.beam_idx = w.beam_idx; dc.beam_div = w.beam_div; dc.beam_state = w.beam_state;
     dc.bpool = w.bpool; dc.assign = w.assign; dc.out_len = out_len; dc.out_scores = out_scores;
+    if (K == 1 && token_scores) {      // columns an image does not reach (after its EOS) hold 0
+        dc.token_scores = token_scores;
+        mg_memset_async(token_scores, 0, (size_t)N * (max_length - 1) * sizeof(float), st);
+    }
+    dc.nbest = BeamOut{num_return, opts ? opts->beam_indices : nullptr, K > 1 ? token_scores : nullptr};
     dc.slots = SlotTable{w.pos, w.img, w.pool, w.ctr, out_len, entries, (int)start};
     // the step as a graph (every step-dependent value lives in the slot table)
     bool graphed = false;
 #ifndef MG_EMU
     if (m->use_graph == 1) {
         const StepGraph::Key key{ws, out_ids, out_len, (const void*)st, slots * 16 + K, L, chunk, max_length, min_length, N * 2 + (early_stopping ? 1 : 0),
-                                 pool_chunks, length_penalty, (const void*)out_scores};     // (B = slots and beams, K = chunk, early_stopping = N and the flag, M_e1 = pool_chunks)
+                                 pool_chunks, length_penalty, (const void*)out_scores, token_scores, dc.nbest.beam_indices, num_return};
+                                 // (B = slots and beams, K = chunk, early_stopping = N and the flag, M_e1 = pool_chunks)
         StepGraph& sg = m->stream_graph;
         if (!(sg.valid && sg.key == key)) {
             std::lock_guard<std::mutex> capture_lock(mg_capture_mutex());
@@ -1767,7 +1806,13 @@ int mg_generate_stream(mg_model* m, void* stream, void* ws, size_t ws_bytes, con
                        const uint8_t* attention_mask, const float* pixel_values, int N, int L, int chunk, int slots, int pool_chunks,
                        int max_length, int min_length, int64_t* out_ids, int32_t* out_len, long* steps_host) {
     return generate_stream_impl(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, N, L, chunk, slots, pool_chunks, 1,
-                                max_length, min_length, 1.0f, 0, out_ids, out_len, nullptr, steps_host, "mg_generate_stream");
+                                max_length, min_length, 1.0f, 0, out_ids, out_len, nullptr, steps_host, "mg_generate_stream", nullptr);
+}
+int mg_generate_stream_scored(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
+                              const uint8_t* attention_mask, const float* pixel_values, int N, int L, int chunk, int slots, int pool_chunks,
+                              int max_length, int min_length, int64_t* out_ids, int32_t* out_len, long* steps_host, const mg_gen_opts* opts) {
+    return generate_stream_impl(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, N, L, chunk, slots, pool_chunks, 1,
+                                max_length, min_length, 1.0f, 0, out_ids, out_len, nullptr, steps_host, "mg_generate_stream", opts);
 }
 int mg_stream_beam_workspace_bytes(const mg_model* m, int chunk, int L, int slots, int pool_chunks, int num_beams, int max_length, size_t* out_bytes) {
     if (!m || !out_bytes || chunk < 1 || L < 1 || slots < 1 || pool_chunks < 2 || num_beams < 1 || num_beams > 8 || max_length < 2)
@@ -1782,7 +1827,16 @@ int mg_generate_stream_beam(mg_model* m, void* stream, void* ws, size_t ws_bytes
                             int num_beams, int max_length, int min_length, float length_penalty, int early_stopping, int64_t* out_ids,
                             int32_t* out_len, float* out_scores, long* steps_host) {
     return generate_stream_impl(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, N, L, chunk, slots, pool_chunks,
-                                num_beams, max_length, min_length, length_penalty, early_stopping, out_ids, out_len, out_scores, steps_host, "mg_generate_stream_beam");
+                                num_beams, max_length, min_length, length_penalty, early_stopping, out_ids, out_len, out_scores, steps_host, "mg_generate_stream_beam",
+                                nullptr);
+}
+int mg_generate_stream_beam_scored(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
+                                   const uint8_t* attention_mask, const float* pixel_values, int N, int L, int chunk, int slots, int pool_chunks,
+                                   int num_beams, int max_length, int min_length, float length_penalty, int early_stopping, int64_t* out_ids,
+                                   int32_t* out_len, long* steps_host, const mg_gen_opts* opts) {
+    return generate_stream_impl(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, N, L, chunk, slots, pool_chunks,
+                                num_beams, max_length, min_length, length_penalty, early_stopping, out_ids, out_len, nullptr, steps_host,
+                                "mg_generate_stream_beam", opts);
 }
 
 // Live timing of the dominant decode kernel (single-query cross-attention over the image K/V stream): when enabled,

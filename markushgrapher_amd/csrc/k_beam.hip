@@ -11,7 +11,7 @@ namespace mg {
 
 struct BeamLayout {
     size_t running_seq, sequences, top_seq, tmp_seq, tmp_idx, running_scores, beam_scores, topv, topi, is_fin, heur, run_idx, beam_idx_out,
-        top_run_idx, flags, rowv, rowi, total;
+        top_run_idx, flags, rowv, rowi, run_lp, lp_out, top_run_lp, tmp_lp, rowlp, toplp, total;
 };
 static BeamLayout beam_layout(int B, int K, int max_len) {
     BeamLayout l;
@@ -35,6 +35,13 @@ static BeamLayout beam_layout(int B, int K, int max_len) {
     l.flags = take((size_t)B * 4 * 4);
     l.rowv = take((size_t)B * K * 2 * K * 4);      // per (image, beam) row: its own top-2K candidates
     l.rowi = take((size_t)B * K * 2 * K * 4);
+    // per-token log-probability histories, beside the beam-index histories (run_idx / beam_idx_out / top_run_idx) and gathered with them
+    l.run_lp = take((size_t)B * K * il * 4);
+    l.lp_out = take((size_t)B * K * il * 4);
+    l.top_run_lp = take((size_t)B * 2 * K * il * 4);
+    l.tmp_lp = take((size_t)B * K * il * 4);
+    l.rowlp = take((size_t)B * K * 2 * K * 4);     // the log-probability (without the running score) of each row candidate
+    l.toplp = take((size_t)B * 2 * K * 4);
     l.total = (off + 255) / 256 * 256;
     return l;
 }
@@ -49,6 +56,7 @@ struct BeamPtrs {
     int *run_idx, *beam_idx_out, *top_run_idx, *flags;
     float* rowv;
     int* rowi;
+    float *run_lp, *lp_out, *top_run_lp, *tmp_lp, *rowlp, *toplp;
 };
 static BeamPtrs beam_ptrs(void* state, int B, int K, int max_len) {
     const BeamLayout l = beam_layout(B, K, max_len);
@@ -60,6 +68,8 @@ static BeamPtrs beam_ptrs(void* state, int B, int K, int max_len) {
     p.topi = (int*)(s + l.topi); p.is_fin = (uint8_t*)(s + l.is_fin); p.heur = (uint8_t*)(s + l.heur);
     p.run_idx = (int*)(s + l.run_idx); p.beam_idx_out = (int*)(s + l.beam_idx_out); p.top_run_idx = (int*)(s + l.top_run_idx);
     p.flags = (int*)(s + l.flags); p.rowv = (float*)(s + l.rowv); p.rowi = (int*)(s + l.rowi);
+    p.run_lp = (float*)(s + l.run_lp); p.lp_out = (float*)(s + l.lp_out); p.top_run_lp = (float*)(s + l.top_run_lp);
+    p.tmp_lp = (float*)(s + l.tmp_lp); p.rowlp = (float*)(s + l.rowlp); p.toplp = (float*)(s + l.toplp);
     return p;
 }
 
@@ -76,6 +86,8 @@ __global__ __launch_bounds__(256) void beam_init_kernel(BeamPtrs p, int B, int K
     for (int i = tid; i < K * (max_len - 1); i += 256) {
         p.run_idx[(size_t)b * K * (max_len - 1) + i] = -1;
         p.beam_idx_out[(size_t)b * K * (max_len - 1) + i] = -1;
+        p.run_lp[(size_t)b * K * (max_len - 1) + i] = 0.f;
+        p.lp_out[(size_t)b * K * (max_len - 1) + i] = 0.f;
     }
     for (int i = tid; i < K; i += 256) {
         p.running_scores[b * K + i] = i == 0 ? 0.f : -1.0e9f;
@@ -203,7 +215,17 @@ __global__ __launch_bounds__(BT_THREADS) void beam_row_topk_kernel(BeamPtrs p, c
             if (cand_before(selv[ww], seli[ww], bv, bi)) { bv = selv[ww]; bi = seli[ww]; }
         __syncthreads();
         lastv = bv; lasti = bi;
-        if (tid == 0) { p.rowv[(size_t)row * keep + round] = bv; p.rowi[(size_t)row * keep + round] = bi; }
+        if (tid == 0) {
+            p.rowv[(size_t)row * keep + round] = bv; p.rowi[(size_t)row * keep + round] = bi;
+            // the candidate's processed log-probability, by the same operations as its value above (not bv - rs: that loses bits)
+            const int v = bi - k * V;
+            float lp = -INFINITY;
+            if (v >= 0 && v < V) {
+                lp = (lg[v] - mx) - lse;
+                if (no_eos && v == eos) lp = -INFINITY;
+            }
+            p.rowlp[(size_t)row * keep + round] = lp;
+        }
     }
 }
 // rank of every row candidate among the image's K*2K; ranks < 2K are the image's top-2K in order
@@ -218,7 +240,7 @@ __global__ __launch_bounds__(128) void beam_merge_topk_kernel(BeamPtrs p, int K,
     if (tid < n) {
         int rank = 0;
         for (int j = 0; j < n; ++j) rank += cand_before(cv[j], ci[j], cv[tid], ci[tid]) ? 1 : 0;
-        if (rank < keep) { p.topv[b * keep + rank] = cv[tid]; p.topi[b * keep + rank] = ci[tid]; }
+        if (rank < keep) { p.topv[b * keep + rank] = cv[tid]; p.topi[b * keep + rank] = ci[tid]; p.toplp[b * keep + rank] = p.rowlp[(size_t)b * n + tid]; }
     }
 }
 
@@ -254,6 +276,9 @@ __global__ __launch_bounds__(256) void beam_update_kernel(BeamPtrs p, int B, int
     int* ri = p.run_idx + (size_t)b * K * il;
     int* bo = p.beam_idx_out + (size_t)b * K * il;
     int* tr = p.top_run_idx + (size_t)b * keep * il;
+    float* rl = p.run_lp + (size_t)b * K * il;
+    float* lo = p.lp_out + (size_t)b * K * il;
+    float* tl = p.top_run_lp + (size_t)b * keep * il;
 
     if (tid < keep) {
         const int idx = p.topi[b * keep + tid];
@@ -274,6 +299,7 @@ __global__ __launch_bounds__(256) void beam_update_kernel(BeamPtrs p, int B, int
         int v = ri[(size_t)src[c] * il + j];
         if (j == cur_len - 1) v = src[c] + b * K;
         tr[(size_t)c * il + j] = v;
+        tl[(size_t)c * il + j] = j == cur_len - 1 ? p.toplp[b * keep + c] : rl[(size_t)src[c] * il + j];
     }
     if (tid < keep) {
         const float tv = p.topv[b * keep + tid];
@@ -323,12 +349,21 @@ __global__ __launch_bounds__(256) void beam_update_kernel(BeamPtrs p, int B, int
     for (int i = tid; i < K * ile; i += 256) {
         const int k = i / ile, j = i - k * ile, s2 = sel[k];
         ti[(size_t)k * il + j] = s2 < K ? bo[(size_t)s2 * il + j] : tr[(size_t)(s2 - K) * il + j];
+        p.tmp_lp[((size_t)b * K + k) * il + j] = s2 < K ? lo[(size_t)s2 * il + j] : tl[(size_t)(s2 - K) * il + j];
     }
     __syncthreads();
     for (int i = tid; i < K * mle; i += 256) { const int k = i / mle, j = i - k * mle; sq[(size_t)k * ml + j] = tq[(size_t)k * ml + j]; }
-    for (int i = tid; i < K * ile; i += 256) { const int k = i / ile, j = i - k * ile; bo[(size_t)k * il + j] = ti[(size_t)k * il + j]; }
+    for (int i = tid; i < K * ile; i += 256) {
+        const int k = i / ile, j = i - k * ile;
+        bo[(size_t)k * il + j] = ti[(size_t)k * il + j];
+        lo[(size_t)k * il + j] = p.tmp_lp[((size_t)b * K + k) * il + j];
+    }
     for (int i = tid; i < K * mle; i += 256) { const int k = i / mle, j = i - k * mle; rs[(size_t)k * ml + j] = ts[(size_t)nxt[k] * ml + j]; }
-    for (int i = tid; i < K * ile; i += 256) { const int k = i / ile, j = i - k * ile; ri[(size_t)k * il + j] = tr[(size_t)nxt[k] * il + j]; }
+    for (int i = tid; i < K * ile; i += 256) {
+        const int k = i / ile, j = i - k * ile;
+        ri[(size_t)k * il + j] = tr[(size_t)nxt[k] * il + j];
+        rl[(size_t)k * il + j] = tl[(size_t)nxt[k] * il + j];
+    }
     __syncthreads();
     if (tid == 0) {
         float nbs[8], nrs[8];
@@ -388,29 +423,45 @@ void beam_step(void* state, const float* logits, int ldl, int V, int B, int K, i
     if (!bs.pos) MG_LAUNCH(beam_flags_kernel, dim3(1), dim3(64), 0, stream, p, B, early_stopping, counters);
 }
 
-// utils.py:3510-3523: best beam per image, generated length from its beam-index history
-__global__ __launch_bounds__(256) void beam_finalize_kernel(BeamPtrs p, int B, int K, int max_len, int64_t* out_ids, int* out_cols,
-                                                       float* out_scores) {
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int ml = max_len, il = max_len - 1;
-    for (int j = tid; j < ml; j += 256) out_ids[(size_t)b * ml + j] = p.sequences[(size_t)b * K * ml + j];
-    int c = 0;
-    for (int j = tid; j < il; j += 256) c += p.beam_idx_out[(size_t)b * K * il + j] != -1;
-    MG_DYN_SMEM(smem);
-    int* tot = (int*)smem;
-    if (tid == 0) *tot = 0;
+// utils.py:3510-3523: the first nr finished hypotheses of state image b (best first) -> output rows o * nr + h; the generated length of each
+// from its beam-index history.  Returns (all threads) the longest returned hypothesis' columns.  smem: nr ints
+MG_DEV int beam_copy_out(const BeamPtrs& p, int b, int K, int max_len, int o, const BeamOut& nb, int64_t* out_ids, float* out_scores, int* cnt) {
+    const int tid = threadIdx.x, ml = max_len, il = max_len - 1, nr = nb.num_return;
+    if (tid < nr) cnt[tid] = 0;
     __syncthreads();
-    if (c) atomicAdd(tot, c);
-    __syncthreads();
-    if (tid == 0) {
-        atomicMax(out_cols, 1 + *tot);
-        if (out_scores) out_scores[b] = p.beam_scores[b * K];
+    for (int h = 0; h < nr; ++h) {
+        const size_t src = (size_t)b * K + h, dst = (size_t)o * nr + h;
+        for (int j = tid; j < ml; j += 256) out_ids[dst * ml + j] = p.sequences[src * ml + j];
+        int c = 0;
+        for (int j = tid; j < il; j += 256) {
+            const int v = p.beam_idx_out[src * il + j];
+            c += v != -1;
+            // stock beam_indices number the rows image * K + beam (the queue form's state numbers them by slot)
+            if (nb.beam_indices) nb.beam_indices[dst * il + j] = v == -1 ? -1 : v + (o - b) * K;
+            if (nb.token_scores) nb.token_scores[dst * il + j] = v == -1 ? 0.f : p.lp_out[src * il + j];
+        }
+        if (c) atomicAdd(cnt + h, c);
+        if (tid == 0 && out_scores) out_scores[dst] = p.beam_scores[src];
     }
+    __syncthreads();
+    int cols = 0;
+    for (int h = 0; h < nr; ++h) cols = cnt[h] + 1 > cols ? cnt[h] + 1 : cols;
+    return cols;
 }
-void beam_finalize(void* state, int B, int K, int max_len, int64_t* out_ids, int* out_cols, float* out_scores, mgStream_t stream) {
+__global__ __launch_bounds__(256) void beam_finalize_kernel(BeamPtrs p, int B, int K, int max_len, int64_t* out_ids, int* out_cols,
+                                                       float* out_scores, BeamOut nb) {
+    MG_DYN_SMEM(smem);
+    const int b = blockIdx.x;
+    const int cols = beam_copy_out(p, b, K, max_len, b, nb, out_ids, out_scores, (int*)smem);
+    if (threadIdx.x == 0) atomicMax(out_cols, cols);
+}
+void beam_finalize(void* state, int B, int K, int max_len, int64_t* out_ids, int* out_cols, float* out_scores, mgStream_t stream,
+                   const BeamOut* nbest) {
     const BeamPtrs p = beam_ptrs(state, B, K, max_len);
+    BeamOut nb = nbest ? *nbest : BeamOut{1, nullptr, nullptr};
+    if (nb.num_return < 1 || nb.num_return > K) nb.num_return = 1;
     mg_memset_async(out_cols, 0, sizeof(int), stream);
-    MG_LAUNCH(beam_finalize_kernel, dim3(B), dim3(256), 16, stream, p, B, K, max_len, out_ids, out_cols, out_scores);
+    MG_LAUNCH(beam_finalize_kernel, dim3(B), dim3(256), 64, stream, p, B, K, max_len, out_ids, out_cols, out_scores, nb);
 }
 
 // ancestor-table reorder: one workgroup per cached position j < t_written, in place
@@ -450,7 +501,7 @@ void beam_reorder_anc(int* anc, const int* beam_idx, int rows, int t_written, co
 //   init   per newly assigned slot: the batch form's initial values (beam_init_kernel), identity ancestors, start tokens
 // ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void beam_slot_end_kernel(BeamPtrs p, int K, int max_len, int early_stopping, int* pos, int* img, int* live,
-                                                       int64_t* out_ids, int* out_len, float* out_scores, int* ctr) {
+                                                       int64_t* out_ids, int* out_len, float* out_scores, int* ctr, BeamOut nb) {
     const int b = blockIdx.x, tid = threadIdx.x;
     if (live[b * K] == 0) return;
     const bool cont = p.flags[b * 4 + 0] && !(p.flags[b * 4 + 1] && early_stopping) && !p.flags[b * 4 + 2];
@@ -459,19 +510,10 @@ __global__ __launch_bounds__(256) void beam_slot_end_kernel(BeamPtrs p, int K, i
         return;
     }
     const int i = img[b * K];
-    const int ml = max_len, il = max_len - 1;
-    for (int j = tid; j < ml; j += 256) out_ids[(size_t)i * ml + j] = p.sequences[(size_t)b * K * ml + j];
-    int c = 0;
-    for (int j = tid; j < il; j += 256) c += p.beam_idx_out[(size_t)b * K * il + j] != -1;
     MG_DYN_SMEM(smem);
-    int* tot = (int*)smem;
-    if (tid == 0) *tot = 0;
-    __syncthreads();
-    if (c) atomicAdd(tot, c);
-    __syncthreads();
+    const int cols = beam_copy_out(p, b, K, max_len, i, nb, out_ids, out_scores, (int*)smem);
     if (tid == 0) {
-        out_len[i] = 1 + *tot;
-        if (out_scores) out_scores[i] = p.beam_scores[b * K];
+        out_len[i] = cols;
         atomicAdd(ctr + 1, 1);
     }
     __syncthreads();
@@ -508,6 +550,8 @@ __global__ __launch_bounds__(256) void beam_slot_init_kernel(BeamPtrs p, int slo
     for (int i = tid; i < K * (max_len - 1); i += 256) {
         p.run_idx[(size_t)b * K * (max_len - 1) + i] = -1;
         p.beam_idx_out[(size_t)b * K * (max_len - 1) + i] = -1;
+        p.run_lp[(size_t)b * K * (max_len - 1) + i] = 0.f;
+        p.lp_out[(size_t)b * K * (max_len - 1) + i] = 0.f;
     }
     for (int i = tid; i < K; i += 256) {
         p.running_scores[b * K + i] = i == 0 ? 0.f : -1.0e9f;
@@ -528,10 +572,13 @@ __global__ __launch_bounds__(256) void beam_slot_init_kernel(BeamPtrs p, int slo
 }
 void beam_slots_step(void* state, int slots, int K, int max_len, int pad, int eos, int start, int early_stopping, int* pos, int* img, int* pool,
                      int* bpool, int* live, int* assign, int64_t* next_ids, int* anc, int T_cap, int pool_cap, int64_t* out_ids, int* out_len,
-                     float* out_scores, int* ctr, bool end_first, mgStream_t stream) {
+                     float* out_scores, int* ctr, bool end_first, mgStream_t stream, const BeamOut* nbest) {
     const BeamPtrs p = beam_ptrs(state, slots, K, max_len);
+    BeamOut nb = nbest ? *nbest : BeamOut{1, nullptr, nullptr};
+    if (nb.num_return < 1 || nb.num_return > K) nb.num_return = 1;
     if (end_first)
-        MG_LAUNCH(beam_slot_end_kernel, dim3(slots), dim3(256), 16, stream, p, K, max_len, early_stopping, pos, img, live, out_ids, out_len, out_scores, ctr);
+        MG_LAUNCH(beam_slot_end_kernel, dim3(slots), dim3(256), 64, stream, p, K, max_len, early_stopping, pos, img, live, out_ids, out_len, out_scores,
+                  ctr, nb);
     MG_LAUNCH(beam_slot_assign_kernel, dim3(1), dim3(64), 0, stream, slots, K, (const int*)live, (const int*)img, assign, ctr);
     MG_LAUNCH(beam_slot_init_kernel, dim3(slots), dim3(256), 0, stream, p, slots, K, max_len, pad ? pad : eos, start, (const int*)assign, pos, img,
               pool, bpool, live, next_ids, anc, T_cap, pool_cap);

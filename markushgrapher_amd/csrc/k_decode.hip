@@ -371,6 +371,13 @@ MG_DEV void top2_merge(float& b1, float& b2, int& i1, float o1, float o2, int oi
     if (o1 > b1 || (o1 == b1 && oi < i1)) { b2 = fmaxf(b1, o2); b1 = o1; i1 = oi; }
     else b2 = fmaxf(b2, o1);
 }
+// log-sum-exp as a (max, sum of exp(x - max)) pair; a pair with sum 0 holds nothing
+MG_DEV void lse_merge(float& m, float& s, float m2, float s2) {
+    if (s2 == 0.f) return;
+    if (s == 0.f) { m = m2; s = s2; }
+    else if (m2 > m) { s = s * expf(m - m2) + s2; m = m2; }
+    else s += s2 * expf(m2 - m);
+}
 __global__ __launch_bounds__(GS_THREADS) void greedy_select_kernel(ArgmaxArgs a) {
     MG_DYN_SMEM(smem);
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -417,10 +424,33 @@ __global__ __launch_bounds__(GS_THREADS) void greedy_select_kernel(ArgmaxArgs a)
     }
     float* rv = (float*)smem;                 // [16][2]
     int* ri = (int*)(smem + 128);             // [16]
+    float* sx = (float*)(smem + 192);         // [1 + 16] token scores: the row's maximum, then the waves' sums
     if (lane == 0) { rv[w * 2] = b1; rv[w * 2 + 1] = b2; ri[w] = i1; }
     __syncthreads();
-    if (tid == 0) {
+    if (tid == 0)
         for (int ww = 1; ww < GS_THREADS / 64; ++ww) top2_merge(b1, b2, i1, rv[ww * 2], rv[ww * 2 + 1], ri[ww]);
+    // token scores: sum of exp(x - max) over the row's processed logits (suppressed stop tokens excluded), a second pass over the row
+    float se = 0.f;
+    if (a.token_scores) {
+        if (tid == 0) sx[0] = b1;
+        __syncthreads();
+        const float mx = sx[0];
+        for (int c = tid; c < nq; c += GS_THREADS) {
+            const float4 q = *(const float4*)(lg + c * 4);
+            const float vv[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int i = c * 4 + j;
+                se += (i < a.V && !(no_eos && is_eos(i))) ? expf(vv[j] - mx) : 0.f;
+            }
+        }
+        se = wave_sum(se);
+        if (lane == 0) sx[1 + w] = se;
+        __syncthreads();
+        if (tid == 0)
+            for (int ww = 1; ww < GS_THREADS / 64; ++ww) se += sx[1 + ww];
+    }
+    if (tid == 0) {
         if (stream) {
             // continuous decoding: the row writes column `pos` of ITS image; a row that ends frees the slot (slot_refill hands
             // it the next image).  Idle slots computed on stale inputs: nothing is written for them.
@@ -430,6 +460,7 @@ __global__ __launch_bounds__(GS_THREADS) void greedy_select_kernel(ArgmaxArgs a)
                 a.next_ids[row] = tok;
                 a.slots.pos[row] = pos;
                 if (pos < a.max_len) a.out_ids[(size_t)img * a.max_len + pos] = tok;
+                if (a.token_scores && pos < a.max_len) a.token_scores[(size_t)img * a.ts_ld + pos - 1] = -logf(se);
                 if (is_eos((int)tok) || pos + 1 >= a.max_len) {
                     a.unfinished[row] = 0;
                     a.slots.img[row] = -1;
@@ -443,6 +474,7 @@ __global__ __launch_bounds__(GS_THREADS) void greedy_select_kernel(ArgmaxArgs a)
         const int64_t tok = unf ? (int64_t)i1 : (int64_t)a.pad;
         a.next_ids[row] = tok;
         if (pos < a.max_len) a.out_ids[(size_t)row * a.max_len + pos] = tok;
+        if (a.token_scores && pos < a.max_len) a.token_scores[(size_t)row * a.ts_ld + pos - 1] = unf ? -logf(se) : 0.f;
         const int still = unf && !is_eos((int)tok);
         a.unfinished[row] = still;
         if (still) atomicAdd(a.n_unfinished, 1);
@@ -522,6 +554,8 @@ __global__ __launch_bounds__(256) void greedy_select_fused_kernel(ArgmaxArgs a) 
     const bool no_eos = a.suppress_eos || pos < a.min_len;
     float b1 = -3.0e38f, b2 = -3.0e38f;
     int i1 = 0x7fffffff;
+    float lm = -3.0e38f, ls = 0.f;                              // token scores: (max, sum) of the row's processed logits
+    const bool want_ts = a.token_scores != nullptr;
     const float4* pt = a.ptop + (size_t)row * a.ntiles;
     for (int c0 = tid; c0 < a.ntiles; c0 += 4 * 256) {          // batches of independent loads (one L2 round trip per batch)
         float4 q[4];
@@ -532,10 +566,17 @@ __global__ __launch_bounds__(256) void greedy_select_fused_kernel(ArgmaxArgs a) 
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) top2_merge(b1, b2, i1, q[u].x, q[u].y, __float_as_int(q[u].z));
+        if (want_ts) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) lse_merge(lm, ls, q[u].x, q[u].w);
+        }
     }
     if (tid < 4 && !no_eos) {                                    // the stop tokens rank with everybody else unless suppressed
         const int e = tid == 0 ? a.eos : (tid - 1 < a.n_eos_more ? a.eos_more[tid - 1] : -1);
-        if (e >= 0) top2_merge(b1, b2, i1, a.stopv[(size_t)row * 4 + tid], -3.0e38f, e);
+        if (e >= 0) {
+            top2_merge(b1, b2, i1, a.stopv[(size_t)row * 4 + tid], -3.0e38f, e);
+            if (want_ts) lse_merge(lm, ls, a.stopv[(size_t)row * 4 + tid], 1.f);      // ... and count in the normaliser
+        }
     }
 #pragma unroll
     for (int step = 1; step < 64; step <<= 1) {
@@ -544,17 +585,29 @@ __global__ __launch_bounds__(256) void greedy_select_fused_kernel(ArgmaxArgs a) 
         top2_merge(b1, b2, i1, o1, o2, oi);
     }
     float* rv = (float*)smem;                 // [4][2]
+    float* rl = (float*)(smem + 32);          // [4][2] token scores: the waves' (max, sum)
     int* ri = (int*)(smem + 64);              // [4], then [8] = the selected token
+    if (want_ts) {
+#pragma unroll
+        for (int step = 1; step < 64; step <<= 1) {
+            const float om = __shfl_xor(lm, step), os = __shfl_xor(ls, step);
+            lse_merge(lm, ls, om, os);
+        }
+        if (lane == 0) { rl[w * 2] = lm; rl[w * 2 + 1] = ls; }
+    }
     if (lane == 0) { rv[w * 2] = b1; rv[w * 2 + 1] = b2; ri[w] = i1; }
     __syncthreads();
     if (tid == 0) {
         for (int ww = 1; ww < 4; ++ww) top2_merge(b1, b2, i1, rv[ww * 2], rv[ww * 2 + 1], ri[ww]);
+        if (want_ts)
+            for (int ww = 1; ww < 4; ++ww) lse_merge(lm, ls, rl[ww * 2], rl[ww * 2 + 1]);
         const int e0 = a.eos, e1 = a.n_eos_more > 0 ? a.eos_more[0] : -1, e2 = a.n_eos_more > 1 ? a.eos_more[1] : -1, e3 = a.n_eos_more > 2 ? a.eos_more[2] : -1;
         const int unf = a.unfinished[row];
         const int64_t tok = unf ? (int64_t)i1 : (int64_t)a.pad;
         a.next_ids[row] = tok;
         ri[8] = (int)tok;
         if (pos < a.max_len) a.out_ids[(size_t)row * a.max_len + pos] = tok;
+        if (want_ts && pos < a.max_len) a.token_scores[(size_t)row * a.ts_ld + pos - 1] = unf ? (b1 - lm) - logf(ls) : 0.f;
         const int t = (int)tok;
         const int still = unf && !(t == e0 || t == e1 || t == e2 || t == e3);
         a.unfinished[row] = still;
@@ -617,7 +670,7 @@ void greedy_select_fused(const ArgmaxArgs& a, mgStream_t stream) {
 }
 
 void greedy_select(const ArgmaxArgs& a, mgStream_t stream) {
-    MG_LAUNCH(greedy_select_kernel, dim3(a.rows), dim3(GS_THREADS), 256, stream, a);
+    MG_LAUNCH(greedy_select_kernel, dim3(a.rows), dim3(GS_THREADS), 512, stream, a);
 }
 
 }  // namespace mg

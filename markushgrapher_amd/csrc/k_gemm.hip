@@ -1060,9 +1060,18 @@ __global__ __launch_bounds__(256) void gemm_rows_splitk_kernel(const uint16_t* X
                     if (x > b1) { b2 = b1; b1 = x; i1 = k; }
                     else b2 = fmaxf(b2, x);
                 }
+                // TopOut::lse: the tile's sum of exp(x - b1) over its non-stop features, again serial in ascending index
+                float se = 0.f;
+                if (top.lse) {
+#pragma unroll
+                    for (int k = 0; k < 32; ++k) {
+                        const float x = rowv[k];
+                        se += x > -3.0e38f ? expf(x - b1) : 0.f;
+                    }
+                }
                 const int jj = lane >> 1, hh = lane & 1;
                 const int m = 32 * i + acc_row(w * 4 + jj, hh);
-                if (m < M) top.ptop[(size_t)m * ntiles + nt] = make_float4(b1, b2, __int_as_float(b1 > -3.0e38f ? nt * 32 + i1 : 0x7fffffff), 0.f);
+                if (m < M) top.ptop[(size_t)m * ntiles + nt] = make_float4(b1, b2, __int_as_float(b1 > -3.0e38f ? nt * 32 + i1 : 0x7fffffff), se);
             }
         }
         __syncthreads();

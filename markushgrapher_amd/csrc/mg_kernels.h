@@ -114,6 +114,9 @@ struct TopOut {
     float* stopv;          // [M][4]
     int stop[4];
     int write_logits;
+    // lse = 1: ptop[..].w = sum over the tile's non-stop features of exp(x - .x) (0 for a tile without one), so that the selection
+    // can merge the (max, sum) pairs into the row's log-sum-exp (token log-probabilities).  0: .w = 0 and every other value as before
+    int lse;
 };
 void gemm_rows_splitk(const uint16_t* X, const uint16_t* W, float* P, int M, int N, int K, int ldp, size_t slab_stride, int KS,
                       const RowScale& rs, mgStream_t stream, const TopOut* top = nullptr);
@@ -412,6 +415,12 @@ struct ArgmaxArgs {
     uint16_t* x2_pk;         // packed window: bf16(h)
     int x2_ld, x2_col0, d;
     float eps;
+    // token log-probabilities (nullable): token_scores[r][pos - 1] = chosen logit - logsumexp(processed logits of the step) for a row that
+    // emits a token at column pos (r = row; continuous decoding: r = the row's image); rows that emit pad (finished) write nothing.
+    // The processed logits are HF's: the stop tokens count in the normaliser only while MinLength does not suppress them.  The
+    // fused form needs the lm_head partials made with TopOut::lse = 1
+    float* token_scores;
+    int ts_ld;               // columns per row of token_scores (max_len - 1)
 };
 void greedy_select(const ArgmaxArgs& a, mgStream_t stream);
 void greedy_select_fused(const ArgmaxArgs& a, mgStream_t stream);
@@ -430,7 +439,17 @@ float beam_length_divisor(int cur_len, float length_penalty);
 void beam_step(void* state, const float* logits, int ldl, int V, int B, int K, int max_len, int cur_len, const int* tdev,
                const float* div_table, int eos, int min_len, float length_penalty, int early_stopping, int64_t* next_ids,
                int* beam_idx, int* counters, mgStream_t stream, const BeamSlots* slots = nullptr);
-void beam_finalize(void* state, int B, int K, int max_len, int64_t* out_ids, int* out_cols, float* out_scores, mgStream_t stream);
+// n-best output of an image's finished hypotheses (best first).  Hypothesis h < num_return of image i is output row i * num_return + h:
+// out_ids [rows][max_len], scores [rows] (sequence scores), and, nullable, beam_indices [rows][max_len - 1] (stock semantics: the flat row
+// image * K + beam each token was chosen from, -1 past the hypothesis' length) and token_scores [rows][max_len - 1] (the processed
+// log-probability of each token, 0 past the length).  The valid width (out_cols / out_len) is the longest returned hypothesis'.
+struct BeamOut {
+    int num_return;
+    int* beam_indices;
+    float* token_scores;
+};
+void beam_finalize(void* state, int B, int K, int max_len, int64_t* out_ids, int* out_cols, float* out_scores, mgStream_t stream,
+                   const BeamOut* nbest = nullptr);
 // ancestor-table form of the KV-cache reorder (cache_utils.py:100-104): anc[j][row] <- anc[j][beam_idx[row]], j < t_written
 void beam_reorder_anc(int* anc, const int* beam_idx, int rows, int t_written, const int* tdev, const int* counters, mgStream_t stream,
                       const BeamSlots* slots = nullptr);
@@ -440,7 +459,7 @@ void beam_reorder_anc(int* anc, const int* beam_idx, int rows, int t_written, co
 // [4] queue head, [5] ready, [7] oldest live image)
 void beam_slots_step(void* state, int slots, int K, int max_len, int pad, int eos, int start, int early_stopping, int* pos, int* img, int* pool,
                      int* bpool, int* live, int* assign, int64_t* next_ids, int* anc, int T_cap, int pool_cap, int64_t* out_ids, int* out_len,
-                     float* out_scores, int* ctr, bool end_first, mgStream_t stream);
+                     float* out_scores, int* ctr, bool end_first, mgStream_t stream, const BeamOut* nbest = nullptr);
 // physical form: dst[lk][row] = src[lk][beam_idx[row]] for nlk = layers*2 K/V planes of [rows][H][t_cap][64] bf16
 void beam_reorder_copy(const uint16_t* src, uint16_t* dst, const int* beam_idx, int nlk, int rows, int H, int t_cap, int t_used,
                        mgStream_t stream);

@@ -28,6 +28,11 @@ class MgError(RuntimeError):
     pass
 
 
+class MgGenOpts(C.Structure):
+    """include/mgrapher.h mg_gen_opts: n-best count and the device buffers of the scored generate calls (NULL = not wanted)."""
+    _fields_ = [("num_return", C.c_int), ("token_scores", C.c_void_p), ("seq_scores", C.c_void_p), ("beam_indices", C.c_void_p)]
+
+
 class TorchMem:
     """Device memory carried by torch tensors on one GPU."""
 
@@ -134,12 +139,16 @@ class Engine:
         L.mg_generate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
                                   C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]
+        L.mg_generate_scored.argtypes = L.mg_generate.argtypes + [C.POINTER(MgGenOpts)]
         L.mg_stream_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         L.mg_generate_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + \
                                         [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.POINTER(C.c_long)]
         L.mg_stream_beam_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         L.mg_generate_stream_beam.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + \
                                              [C.c_int] * 8 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_long)]
+        L.mg_generate_stream_scored.argtypes = L.mg_generate_stream.argtypes + [C.POINTER(MgGenOpts)]
+        L.mg_generate_stream_beam_scored.argtypes = L.mg_generate_stream_beam.argtypes[:-3] + [C.c_void_p, C.POINTER(C.c_long),
+                                                                                               C.POINTER(MgGenOpts)]
         L.mg_stream_encoder_mode.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.mg_debug_bucket_table.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int]
         L.mg_debug_decode_capture.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -375,10 +384,28 @@ class Engine:
         else:
             self._chk(self.lib.mg_stream_encoder_mode(self.model, int(mode), None, 0))
 
+    def _scored_out(self, key, rows, max_length, beams):
+        """Persistent per-shape output buffers of the scored calls (a captured decode step holds their addresses): token scores
+        [rows, max_length - 1] and, for beam search, sequence scores [rows] and beam indices [rows, max_length - 1]."""
+        cache = self.__dict__.setdefault("_gen_sc", {})
+        k = (key, rows, max_length, beams)
+        if k not in cache:
+            if len(cache) > 8:
+                cache.clear()
+            cache[k] = (self.mem.zeros((rows, max_length - 1), np.float32),
+                        self.mem.zeros((rows,), np.float32) if beams else None,
+                        self.mem.zeros((rows, max_length - 1), np.int32) if beams else None)
+        ts, ss, bi = cache[k]
+        opts = MgGenOpts(1, self.mem.ptr(ts).value, self.mem.ptr(ss).value if ss is not None else None,
+                         self.mem.ptr(bi).value if bi is not None else None)
+        return opts, ts, ss, bi
+
     def generate_stream(self, input_ids, bbox, attention_mask, pixel_values, max_length=512, min_length=0, chunk=32, slots=32,
-                        pool_chunks=3):
+                        pool_chunks=3, return_scores=False):
         """Continuous greedy decoding of N images (include/mgrapher.h mg_generate_stream): -> (ids [N, max_length] padded with the pad
-        id, lengths [N] = valid columns, decode steps run).  Row n equals generate()'s row for image n."""
+        id, lengths [N] = valid columns, decode steps run).  Row n equals generate()'s row for image n.
+        return_scores: a fourth item, token_scores [N, max_length - 1] (mg_generate_stream_scored: the log-probability of the token in
+        column j + 1 at column j, 0.0 after the image's EOS)."""
         ids, bb, am, pv, N, L = self._inputs(input_ids, bbox, attention_mask, pixel_values)
         need = C.c_size_t()
         self._chk(self.lib.mg_stream_workspace_bytes(self.model, chunk, L, slots, pool_chunks, C.byref(need)))
@@ -391,16 +418,24 @@ class Engine:
         if out is None:
             out = self._gen_out[okey] = (self.mem.empty((N, max_length), np.int64), self.mem.empty((N,), np.int32))
         steps = C.c_long(0)
-        self._chk(self.lib.mg_generate_stream(self.model, self.mem.stream(), self.mem.ptr(self._sws), self._sws_bytes, self.mem.ptr(ids),
-                                              self.mem.ptr(bb), self.mem.ptr(am) if am is not None else None, self.mem.ptr(pv), N, L, chunk, slots,
-                                              pool_chunks, max_length, min_length, self.mem.ptr(out[0]), self.mem.ptr(out[1]), C.byref(steps)))
-        return self.mem.copy(out[0]), self.mem.copy(out[1]), int(steps.value)
+        args = (self.model, self.mem.stream(), self.mem.ptr(self._sws), self._sws_bytes, self.mem.ptr(ids), self.mem.ptr(bb),
+                self.mem.ptr(am) if am is not None else None, self.mem.ptr(pv), N, L, chunk, slots, pool_chunks, max_length, min_length,
+                self.mem.ptr(out[0]), self.mem.ptr(out[1]), C.byref(steps))
+        if not return_scores:
+            self._chk(self.lib.mg_generate_stream(*args))
+            return self.mem.copy(out[0]), self.mem.copy(out[1]), int(steps.value)
+        opts, ts, _, _ = self._scored_out("stream", N, max_length, False)
+        self._chk(self.lib.mg_generate_stream_scored(*args, C.byref(opts)))
+        return self.mem.copy(out[0]), self.mem.copy(out[1]), int(steps.value), self.mem.copy(ts)
 
     def generate_stream_beam(self, input_ids, bbox, attention_mask, pixel_values, num_beams=5, max_length=512, min_length=0,
-                             length_penalty=1.0, early_stopping=False, chunk=32, slots=32, pool_chunks=3):
+                             length_penalty=1.0, early_stopping=False, chunk=32, slots=32, pool_chunks=3, num_return=1, return_scores=False):
         """Continuous BEAM-SEARCH decoding of N images (include/mgrapher.h mg_generate_stream_beam): `slots` image slots of num_beams
         rows -> (ids [N, max_length] = best hypothesis per image, lengths [N], scores [N], decode steps run).  Row n equals
-        generate(num_beams=...)'s result for image n."""
+        generate(num_beams=...)'s result for image n.
+        num_return > 1: the n-best list - ids [N * num_return, max_length] and scores [N * num_return] (hypotheses of an image consecutive,
+        best first), lengths [N] = the longest returned hypothesis' columns.  return_scores: a fifth item, {"token_scores", "beam_indices"}
+        [N * num_return, max_length - 1] (mg_generate_stream_beam_scored)."""
         ids, bb, am, pv, N, L = self._inputs(input_ids, bbox, attention_mask, pixel_values)
         if slots * num_beams > self.MAX_LIVE_ROWS:
             raise MgError(f"generate_stream_beam: slots * num_beams = {slots * num_beams} rows exceed the supported {self.MAX_LIVE_ROWS}")
@@ -410,12 +445,29 @@ class Engine:
             self._sws = None
             self._sws = self.mem.empty((need.value,), np.uint8)
             self._sws_bytes = need.value
-        okey = ("stream-beam", N, max_length)
+        nr = int(num_return)
+        if not 1 <= nr <= num_beams:
+            raise ValueError(f"num_return must be in [1, num_beams = {num_beams}], got {nr}")
+        okey = ("stream-beam", N * nr, max_length)
         out = self._gen_out.get(okey)
         if out is None:
-            out = self._gen_out[okey] = (self.mem.empty((N, max_length), np.int64), self.mem.empty((N,), np.int32),
-                                         self.mem.empty((N,), np.float32))
+            out = self._gen_out[okey] = (self.mem.empty((N * nr, max_length), np.int64), self.mem.empty((N,), np.int32),
+                                         self.mem.empty((N * nr,), np.float32))
         steps = C.c_long(0)
+        if nr > 1 or return_scores:
+            opts, ts, ss, bi = self._scored_out("stream-beam", N * nr, max_length, True)
+            opts.num_return = nr
+            if not return_scores:
+                opts.token_scores = opts.beam_indices = None
+            self._chk(self.lib.mg_generate_stream_beam_scored(
+                self.model, self.mem.stream(), self.mem.ptr(self._sws), self._sws_bytes, self.mem.ptr(ids), self.mem.ptr(bb),
+                self.mem.ptr(am) if am is not None else None, self.mem.ptr(pv), N, L, chunk, slots, pool_chunks, num_beams, max_length,
+                min_length, C.c_float(length_penalty), 1 if early_stopping else 0, self.mem.ptr(out[0]), self.mem.ptr(out[1]), C.byref(steps),
+                C.byref(opts)))
+            res = (self.mem.copy(out[0]), self.mem.copy(out[1]), self.mem.copy(ss), int(steps.value))
+            if return_scores:
+                res += ({"token_scores": self.mem.copy(ts), "beam_indices": self.mem.copy(bi)},)
+            return res
         self._chk(self.lib.mg_generate_stream_beam(self.model, self.mem.stream(), self.mem.ptr(self._sws), self._sws_bytes, self.mem.ptr(ids),
                                                    self.mem.ptr(bb), self.mem.ptr(am) if am is not None else None, self.mem.ptr(pv), N, L, chunk,
                                                    slots, pool_chunks, num_beams, max_length, min_length, C.c_float(length_penalty),
@@ -424,8 +476,15 @@ class Engine:
         return self.mem.copy(out[0]), self.mem.copy(out[1]), self.mem.copy(out[2]), int(steps.value)
 
     def generate(self, input_ids, bbox, attention_mask, pixel_values, num_beams=1, max_length=512, min_length=0,
-                 length_penalty=1.0, early_stopping=False, return_top2=False, e1=None):
+                 length_penalty=1.0, early_stopping=False, return_top2=False, e1=None, num_return=1, return_scores=False):
+        """-> (ids [B, cols], scores [B] (beam: sequences_scores), top2 or None).  num_return (beam: 1 .. num_beams): the n-best list,
+        ids [B * num_return, cols] and scores [B * num_return], hypotheses of an image consecutive, best first; cols = the longest
+        returned hypothesis'.  return_scores: a fourth item {"token_scores": [rows, cols - 1], "beam_indices": [rows, cols - 1] (beam) or
+        None} - include/mgrapher.h mg_generate_scored."""
         ids, bb, am, pv, B, L = self._inputs(input_ids, bbox, attention_mask, pixel_values)
+        nr = int(num_return)
+        if not 1 <= nr <= num_beams:
+            raise ValueError(f"num_return must be in [1, num_beams = {num_beams}], got {nr}")
         e1t, M = self._e1(e1, B)
         if B * num_beams > self.MAX_LIVE_ROWS:
             raise MgError(f"generate: B * num_beams = {B * num_beams} live sequences exceeds the supported "
@@ -433,18 +492,30 @@ class Engine:
         ws, nb = self.workspace(B, L, num_beams, max_length, 0, M)
         # the id buffer is persistent per (B, max_length): the captured decode-step graph holds its address, so a stable
         # buffer lets later calls replay the graph instead of re-capturing; callers get a copy
-        okey = (B, max_length)
+        okey = (B * nr, max_length)
         out = self._gen_out.get(okey)
         if out is None:
             self._gen_out.clear()
-            out = self._gen_out[okey] = self.mem.empty((B, max_length), np.int64)
-        scores = self.mem.zeros((B,), np.float32)
+            out = self._gen_out[okey] = self.mem.empty((B * nr, max_length), np.int64)
+        scores = self.mem.zeros((B * nr,), np.float32)
         top2 = self.mem.zeros((max_length, B * num_beams, 2), np.float32) if (return_top2 and num_beams == 1) else None
         cols = C.c_int(0)
-        self._chk(self.lib.mg_generate(self.model, self.mem.stream(), self.mem.ptr(ws), nb, self.mem.ptr(ids), self.mem.ptr(bb),
-                                       self.mem.ptr(am) if am is not None else None, self.mem.ptr(pv),
-                                       self.mem.ptr(e1t) if e1t is not None else None, M, B, L, num_beams,
-                                       max_length, min_length, C.c_float(length_penalty), 1 if early_stopping is True else 0,
-                                       self.mem.ptr(out), C.byref(cols), self.mem.ptr(scores),
-                                       self.mem.ptr(top2) if top2 is not None else None))
-        return self.mem.copy(out[:, :cols.value]), scores, top2
+        args = (self.model, self.mem.stream(), self.mem.ptr(ws), nb, self.mem.ptr(ids), self.mem.ptr(bb),
+                self.mem.ptr(am) if am is not None else None, self.mem.ptr(pv), self.mem.ptr(e1t) if e1t is not None else None, M, B, L,
+                num_beams, max_length, min_length, C.c_float(length_penalty), 1 if early_stopping is True else 0,
+                self.mem.ptr(out), C.byref(cols), self.mem.ptr(scores), self.mem.ptr(top2) if top2 is not None else None)
+        if nr == 1 and not return_scores:
+            self._chk(self.lib.mg_generate(*args))
+            return self.mem.copy(out[:, :cols.value]), scores, top2
+        beam = num_beams > 1
+        opts, ts, _, bi = self._scored_out("batch", B * nr, max_length, beam)
+        opts.num_return = nr
+        opts.seq_scores = self.mem.ptr(scores).value if beam else None
+        if not return_scores:
+            opts.token_scores = opts.beam_indices = None
+        self._chk(self.lib.mg_generate_scored(*args, C.byref(opts)))
+        n = cols.value
+        res = (self.mem.copy(out[:, :n]), scores, top2)
+        if return_scores:
+            res += ({"token_scores": self.mem.copy(ts[:, :n - 1]), "beam_indices": self.mem.copy(bi[:, :n - 1]) if beam else None},)
+        return res

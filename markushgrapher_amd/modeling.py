@@ -85,6 +85,28 @@ class Seq2SeqLMOutput:
         return (self.loss, self.logits)[i] if self.loss is not None else (self.logits,)[i]
 
 
+@dataclass
+class GenerateOutput:
+    """generate(return_dict_in_generate=True): the fields of stock GenerateEncoderDecoderOutput / GenerateBeamEncoderDecoderOutput that
+    this path fills, plus `token_scores`.
+      sequences         [B * num_return_sequences, T]
+      sequences_scores  [B * num_return_sequences] (beam search)
+      beam_indices      [B * num_return_sequences, T - 1] (beam search; -1 past a hypothesis' length)
+      scores / logits   tuples of T - 1 tensors [B * num_beams, vocab] (output_scores / output_logits only; see generate())
+      token_scores      [B * num_return_sequences, T - 1], computed on the device beside the ids: greedy = compute_transition_scores(
+                        normalize_logits=True), beam = compute_transition_scores(beam_indices=..., normalize_logits=False); 0.0 after a
+                        row's EOS / past a hypothesis' length"""
+    sequences: torch.Tensor
+    sequences_scores: Optional[torch.Tensor] = None
+    beam_indices: Optional[torch.Tensor] = None
+    scores: Optional[tuple] = None
+    logits: Optional[tuple] = None
+    token_scores: Optional[torch.Tensor] = None
+
+    def __getitem__(self, k):
+        return getattr(self, k)
+
+
 class _ParamTree(nn.Module):
     """nn.Module tree built from dotted state-dict keys, so `.encoder.block[0]...`, `.decoder`, `.lm_head` exist with
     the HF names and carry state_dict()/parameters()."""
@@ -394,6 +416,14 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
         size 1), which is what is reproduced here; pass a mask explicitly for padded batches."""
         if do_sample:
             raise NotImplementedError("sampling is not part of the reference's decode path")
+        num_return = int(kw.pop("num_return_sequences", None) or 1)
+        as_dict = bool(kw.pop("return_dict_in_generate", False))
+        want_scores, want_logits = bool(kw.pop("output_scores", False)), bool(kw.pop("output_logits", False))
+        num_beams = int(num_beams)
+        if num_beams == 1 and num_return > 1:
+            raise ValueError(f"Greedy methods without beam search do not support `num_return_sequences` different than 1 (got {num_return}).")
+        if num_return > num_beams:
+            raise ValueError("`num_return_sequences` has to be smaller or equal to `num_beams`.")
         self._check_e1(e1)
         eng = self._eng()
         max_length = int(max_length or self.config.max_length)
@@ -403,10 +433,59 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
                 attention_mask = (input_ids != pad).long()
             else:
                 attention_mask = torch.ones_like(input_ids)
-        ids, _, _ = eng.generate(input_ids, bbox, attention_mask, pixel_values, num_beams=int(num_beams),
-                                 max_length=max_length, min_length=int(min_length), length_penalty=float(length_penalty),
-                                 early_stopping=early_stopping, e1=e1)
-        return ids
+        gkw = dict(num_beams=num_beams, max_length=max_length, min_length=int(min_length), length_penalty=float(length_penalty),
+                   early_stopping=early_stopping, e1=e1)
+        if not as_dict:
+            ids, _, _ = eng.generate(input_ids, bbox, attention_mask, pixel_values, num_return=num_return, **gkw)
+            return ids
+        cap = None
+        if want_scores or want_logits:
+            # every step's pre-selection logits through the parity instrumentation (eager launches of the same kernels, same ids)
+            B = int(input_ids.shape[0])
+            cap = eng.debug_decode_capture(max_length - 1, B * num_beams)
+        try:
+            ids, seq_scores, _, ex = eng.generate(input_ids, bbox, attention_mask, pixel_values, num_return=num_return, return_scores=True,
+                                                  **gkw)
+        finally:
+            if cap is not None:
+                eng.debug_decode_capture()
+        out = GenerateOutput(sequences=ids, token_scores=ex["token_scores"])
+        if num_beams > 1:
+            out.sequences_scores, out.beam_indices = seq_scores, ex["beam_indices"].long()
+        if cap is not None:
+            steps = int(ids.shape[1]) - 1
+            raw = cap[:steps]
+            if want_logits:
+                out.logits = tuple(raw[t].clone() for t in range(steps))
+            if want_scores:
+                # stock's processed scores: log-softmax first for beam search (utils.py:3388-3389), then MinLength (EOS at -inf while
+                # the sequence is shorter than min_length)
+                sc = torch.log_softmax(raw, dim=-1) if num_beams > 1 else raw.clone()
+                eos = self.config.eos_token_id
+                for t in range(min(steps, max(0, int(min_length) - 1))):
+                    sc[t, :, eos] = -float("inf")
+                out.scores = tuple(sc[t] for t in range(steps))
+        return out
+
+    def compute_transition_scores(self, sequences, scores, beam_indices=None, normalize_logits=False):
+        """Stock GenerationMixin.compute_transition_scores (generation/utils.py): the score of every generated token from generate()'s
+        `scores` (output_scores=True) -> [rows, generated length].  Greedy: normalize_logits=True gives the token log-probabilities (what
+        GenerateOutput.token_scores holds without the full-vocab scores); beam: pass beam_indices, normalize_logits=False."""
+        if beam_indices is None:
+            beam_indices = torch.arange(scores[0].shape[0], device=sequences.device).view(-1, 1).expand(-1, len(scores))
+        V = scores[0].shape[-1]
+        stacked = torch.stack(scores).reshape(len(scores), -1).transpose(0, 1)
+        if normalize_logits:
+            stacked = torch.log_softmax(stacked.reshape(-1, V, stacked.shape[-1]), dim=1).reshape(-1, stacked.shape[-1])
+        mask = beam_indices < 0
+        max_len = int((1 - mask.long()).sum(-1).max())
+        beam_indices = beam_indices.clone()[:, :max_len]
+        mask = mask[:, :max_len]
+        beam_indices[mask] = 0
+        indices = sequences[:, sequences.shape[-1] - max_len:].to(stacked.device) + beam_indices.to(stacked.device) * V
+        out = stacked.gather(0, indices)
+        out[mask.to(out.device)] = 0
+        return out
 
     @torch.no_grad()
     def in_flight(self, n: int = 4):
@@ -418,7 +497,7 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
         return InFlight(self._eng(), n)
 
     def generate_queue(self, encodings, max_length=None, min_length=0, slots=32, chunk=32, contexts=1, num_beams=1, length_penalty=1.0,
-                       early_stopping=False):
+                       early_stopping=False, num_return_sequences=1, return_scores=False):
         """The reference's evaluation loop (ref: utils/ocsr/utils_evaluation.py:140-285) as ONE call: `encodings` = the per-sample
         dicts it builds (input_ids [1, L_n] or [L_n], bbox, pixel_values; attention_mask / labels ignored as there), greedy,
         max_length as there.  Returns a list of 1-D id tensors - predictions[n] == self.generate(**encodings[n], num_beams=1,
@@ -428,7 +507,11 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
         at most 4) at the same time - same ids, 1.4 x the images/s at 4.
         num_beams > 1 (the reference's shipped setting, config/predict.yaml beam_search: True -> 5): the beam queue (mg_generate_stream_beam,
         `slots` image slots of num_beams rows, slots * num_beams <= 256); predictions[n] == self.generate(**encodings[n],
-        num_beams=num_beams, ...)[0]."""
+        num_beams=num_beams, ...)[0].
+        return_scores or num_return_sequences > 1: one dict per image instead - "sequences" [num_return_sequences, T] (the n-best list,
+        best first, T = the longest returned hypothesis' columns), "token_scores" [num_return_sequences, T - 1] (as generate()'s
+        GenerateOutput.token_scores) and, for beam search, "sequences_scores" [num_return_sequences] and "beam_indices" (numbered as if
+        the image were decoded alone)."""
         from .assembly import collate_for_generate
         self._check_e1(None)
         eng = self._eng()
@@ -441,21 +524,48 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
         pix = torch.cat([torch.as_tensor(e["pixel_values"]).reshape(1, *torch.as_tensor(e["pixel_values"]).shape[-3:]) for e in encodings]).to(self.device)
         n = len(feats)
         num_beams = int(num_beams)
+        nr = int(num_return_sequences or 1)
+        if num_beams == 1 and nr > 1:
+            raise ValueError(f"Greedy methods without beam search do not support `num_return_sequences` different than 1 (got {nr}).")
+        if nr > num_beams:
+            raise ValueError("`num_return_sequences` has to be smaller or equal to `num_beams`.")
+        scored = bool(return_scores) or nr > 1
         if num_beams > 1:
             slots = max(1, min(int(slots), 256 // num_beams))
 
         def run(ctx, sl):
             m = sl.stop - sl.start
             if num_beams > 1:
-                o, l, _, _ = ctx.generate_stream_beam(batch["input_ids"][sl], batch["bbox"][sl], batch["attention_mask"][sl], pix[sl],
-                                                      num_beams=num_beams, max_length=max_length, min_length=int(min_length),
-                                                      length_penalty=float(length_penalty), early_stopping=bool(early_stopping),
-                                                      chunk=min(chunk, m), slots=min(slots, m), pool_chunks=3)
+                r = ctx.generate_stream_beam(batch["input_ids"][sl], batch["bbox"][sl], batch["attention_mask"][sl], pix[sl],
+                                             num_beams=num_beams, max_length=max_length, min_length=int(min_length),
+                                             length_penalty=float(length_penalty), early_stopping=bool(early_stopping),
+                                             chunk=min(chunk, m), slots=min(slots, m), pool_chunks=3, num_return=nr, return_scores=scored)
+                o, l = r[0], r[1]
             else:
-                o, l, _ = ctx.generate_stream(batch["input_ids"][sl], batch["bbox"][sl], batch["attention_mask"][sl], pix[sl],
-                                              max_length=max_length, min_length=int(min_length), chunk=min(chunk, m), slots=min(slots, m),
-                                              pool_chunks=3)
+                r = ctx.generate_stream(batch["input_ids"][sl], batch["bbox"][sl], batch["attention_mask"][sl], pix[sl],
+                                        max_length=max_length, min_length=int(min_length), chunk=min(chunk, m), slots=min(slots, m),
+                                        pool_chunks=3, return_scores=scored)
+                o, l = r[0], r[1]
+            if scored:
+                return o, l, r
             return o, l
+
+        def per_image(o, l, r):
+            # o [m * nr, max_length]; the queue's beam indices number the rows of the part's images: renumbered as if each image were alone
+            l = l.cpu().tolist()
+            res = []
+            for i, li in enumerate(l):
+                rows = slice(i * nr, (i + 1) * nr)
+                d = {"sequences": o[rows, :li]}
+                if num_beams > 1:
+                    d["sequences_scores"] = r[2][rows]
+                    bi = r[4]["beam_indices"][rows, :li - 1].long()
+                    d["beam_indices"] = torch.where(bi >= 0, bi - i * num_beams, bi)
+                    d["token_scores"] = r[4]["token_scores"][rows, :li - 1]
+                else:
+                    d["token_scores"] = r[3][i:i + 1, :li - 1]
+                res.append(d)
+            return res
         contexts = max(1, min(int(contexts), 4, n // max(1, min(slots, n))))
         prev = eng.set_padding_semantics(True)
         try:
@@ -474,13 +584,20 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
                     return run(ctx, slice(i * per, min(n, (i + 1) * per)))
                 outs = self._inflight.map(part, range(-(-n // per)))
                 rows = []
-                for o, l in outs:
+                for res in outs:
+                    if scored:
+                        rows += per_image(*res)
+                        continue
+                    o, l = res
                     l = l.cpu().tolist()
                     rows += [o[i, :l[i]] for i in range(len(l))]
                 return rows
-            ids, lens = run(eng, slice(0, n))
+            res = run(eng, slice(0, n))
         finally:
             eng.set_padding_semantics(prev)
+        if scored:
+            return per_image(*res)
+        ids, lens = res
         lens = lens.cpu().tolist()
         return [ids[i, :lens[i]] for i in range(len(lens))]
 
