@@ -11,19 +11,24 @@ Every rank keeps --inflight (default 4) execution contexts going at once (mg_clo
 stream / host thread), and a call of a context takes up to --batches-per-call (default 5) batches of 32 side by side (the decode
 step then reads the decoder's weights once for all of them): the K timed steps are cut into near-equal calls over the contexts
 (inflight.plan_calls: 20 steps = one call of 5 batches per context), all of them start and end inside the timed region, every
-batch's ids are bit-identical to a call on the batch alone (tests/test_engine.py, tests/test_inflight.py; checked in every run:
+batch's ids are bit-identical to a call on the batch alone (tests/test_engine.py, tests/test_inflight.py; checked with --full:
 config.ids_equal_one_batch_calls).  `one_call_alone` repeats the largest call shape on one context, `one_batch_in_flight` the
 one-batch-at-a-time loop of the reference.
 
-    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run does what the headline needs: set-up, warm-up, the timed regions, --dump-outputs, the result line.  --full goes on to
+every side measurement and check listed under the result line below (their keys are null without it).  The timed regions are
+the same in both modes.
 
 --dump-outputs DIR: after the timed regions, rank 0 writes what the last timed step handed its caller, as float64 .npy files
 (exact for token ids): ids.npy [batch, new_tokens + 1] (that batch's generate() ids on rank 0), gathered_ids.npy [batch x N, 512]
 and gathered_lengths.npy [batch x N] (the id exchange's all-gathered block of that step, pad-filled).  The inputs and weights are seeded, so
 two builds run with the same arguments can be compared array for array.
 
-Prints ONE JSON line on rank 0:
+Prints ONE JSON line on rank 0: `value` / `ms_per_step` (median timed region), the spread over the regions, host CPU use and the
+configuration; with --full also
   roofline       dominant kernel (single-query cross-attention over the per-image K/V stream), algorithmic bytes / average
                  launch duration from HIP events on the launch stream of the first context during the timed region (i.e. beside
                  the other batches' kernels); `traffic` = HBM bytes per launch from a FETCH_SIZE pass (rocprofv3 --pmc, run by this
@@ -32,8 +37,10 @@ Prints ONE JSON line on rank 0:
   one_batch_in_flight   one batch per call on one context: images/s, the kernel's and the phases' figures (the loop of rounds 1-2)
   phases         encoder (MFMA-bound) and decode step (HBM-bound) against their own rooflines: enc_mfma_frac, dec_hbm_frac,
                  dec_mfma_frac (SURVEY.md §8d formulas), phase times from HIP events inside mg_generate
+  with_e1_branch the timed plan again with the OCSR vision branch attached
   extra_runs     EOS-enabled greedy run (max_length 512) and beam-5 (BASELINE configs[2]) on the same inputs
   cpu_baseline   the fp32 CPU oracle (oracle/udop_oracle.py, kind "port") on a bounded sample on this box's host cores
+  config.ids_equal_one_batch_calls   every batch of the last timed call against a call on that batch alone
 """
 import argparse
 import ctypes as C
@@ -302,6 +309,18 @@ def pmc_traffic(args, nb=1):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def bench_batch(shape, B, seed):
+    """synth.synth_batch(shape, B, seed=seed, return_pages=True) without its host pixel_values, which the step never reads (it resizes
+    the pages on the device) and which cost ~1.8 s of host time per batch of 32 1024 px pages.  synth_batch's text fields do not depend
+    on the page size: they come from a call on 64 px pages, the pages from synth_pages_u8 with synth_batch's own size and seed
+    (tests/test_bench_config.py pins the equality)."""
+    from markushgrapher_amd import synth
+    out = synth.synth_batch(shape, B, seed=seed, page_px=64)
+    del out["pixel_values"]
+    out["pages_u8"] = synth.synth_pages_u8(B, 2 * shape.image_size, seed)
+    return out
+
+
 def dump_outputs(dirname, arrays):
     """--dump-outputs: one float64 DIR/<name>.npy per array (token ids and lengths are exact in float64; 1 MB at 8 GPUs)."""
     out = {k: v.cpu().numpy().astype(np.float64) for k, v in arrays.items()}
@@ -348,9 +367,11 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--new-tokens", type=int, default=256)
     ap.add_argument("--beams", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-runs", action="store_true", help="skip the EOS-enabled and beam-5 side measurements")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 FETCH_SIZE child pass")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every side measurement and check (module docstring); without it their keys are null")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baselines")
+    ap.add_argument("--no-extra-runs", action="store_true", help="with --full: skip the OCSR-branch, EOS-enabled, beam-5 and configs[4] side measurements")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the rocprofv3 FETCH_SIZE child pass")
     ap.add_argument("--pmc-child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--pmc-batches", type=int, default=1, help=argparse.SUPPRESS)
     ap.add_argument("--profile-every", type=int, default=16)
@@ -420,8 +441,9 @@ def main():
     # DIFFERENT images in every batch of the timed region: batch j of this rank is drawn with its own seed (j = 0: the batch the parity
     # fixture tests/golden/g4_bench.npz pins), all batches padded to the pool's longest text (ids 0 / box 0 / mask 0, as the reference's
     # collator pads: ref core/trainers/data_collator.py:55-108), so that a call really holds 160 different images at a common L_max
+    t0 = time.time()
     n_pool = max(1, min(args.steps, int(os.environ.get("MG_BENCH_DISTINCT", "20"))))
-    pool_np = [synth.synth_batch(shape, B, seed=synth.BENCH_SEED + rank + 1000 * j, return_pages=True) for j in range(n_pool)]
+    pool_np = [bench_batch(shape, B, seed=synth.BENCH_SEED + rank + 1000 * j) for j in range(n_pool)]
     L = max(p_["input_ids"].shape[1] for p_ in pool_np)
     for p_ in pool_np:
         padn = L - p_["input_ids"].shape[1]
@@ -432,6 +454,7 @@ def main():
     dtypes = {"input_ids": np.int64, "bbox": np.float32, "attention_mask": np.uint8, "pixel_values": np.float32, "pages_u8": np.uint8}
     pool = [{k: eng.mem.asarray(v, dtypes[k]) for k, v in p_.items() if k != "pixel_values"} for p_ in pool_np]
     inp, dev = pool_np[0], pool[0]
+    t_inputs = time.time() - t0
     # the exchange: static [B, 512] int32 ids + [B] int32 lengths per rank, posted asynchronously and
     # double-buffered (markushgrapher_amd/dist.py), so the gather of batch i overlaps the encoder of batch i+1
     # (at world == 1 the exchange degenerates to its single-rank copy path, which runs all the same: the packing of the static
@@ -520,6 +543,7 @@ def main():
     # on len(fl) different contexts), then whole plans until at least `warmup` batches have run
     timed_plan = plan_calls(args.steps)
     torch.cuda.synchronize()
+    t0 = time.time()
     if args.warmup:
         warmed = 0
         for nb_ in sorted(set(timed_plan)):
@@ -530,6 +554,7 @@ def main():
             warmed += args.steps
     while handles:
         ex.wait(handles.pop(0))
+    t_warmup = time.time() - t0
     # live timing of the dominant kernel on the launch stream (HIP events), sampled every N-th decode step; phase events
     L_ = eng.lib
     L_.mg_profile_cross_attention.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -553,7 +578,9 @@ def main():
         L_.mg_profile_phases(eng.model, 0)
         return n_l, ms, keys, empty_ms, n_ph, enc_ms, dec_ms
 
-    profile_on()                       # on the first context: its launches are bracketed while the other contexts run beside it
+    # on the first context: its launches are bracketed while the other contexts run beside it.  On in a plain run too, although only
+    # --full reads the figures: the timed regions stay the same launches in both modes
+    profile_on()
     import resource
     import threading
     repeats = max(1, args.repeats)
@@ -581,6 +608,8 @@ def main():
         dts.append(dt)
         cpu_s.append((ru1.ru_utime - ru0.ru_utime) + (ru1.ru_stime - ru0.ru_stime))
     dt = float(np.median(dts))         # `value` = the median region
+    # the timed calls' cross-attention form
+    absorbed_main = args.beams == 1 and (eng.cross_absorb is True or (eng.cross_absorb == "auto" and int(round(nb_first)) * B >= eng.ABSORB_AUTO_ROWS))
     if args.dump_outputs and rank == 0:
         # the exchange's receive block is reused by the next post: copied out here, before any side run
         dump_outputs(args.dump_outputs, {"ids": ids, "gathered_ids": all_ids, "gathered_lengths": all_len})
@@ -597,7 +626,7 @@ def main():
     solo_call = None
     ids_call, first_call = last_call[0]
     ids_equal_solo = None
-    if (len(fl) > 1 or bpc > 1) and rank == 0:
+    if args.full and (len(fl) > 1 or bpc > 1) and rank == 0:
         eng.set_shared_gpu(False)        # the context runs alone from here on (InFlight had set it: mg_set_shared_gpu)
         # every batch of the last timed call against ONE call on that batch alone (one context, one batch per call, same padded length)
         eq = []
@@ -645,7 +674,7 @@ def main():
     # 384 px + MLP projector, csrc/swin.hip) attached to every context, evaluated inside the timed step from the step's own pixel_values,
     # the decoder cross-attending over [144 e1 tokens | VTL states].  Same plan, same inputs, same clock as the headline region.
     e1_run = None
-    if rank == 0 and world == 1 and args.beams == 1 and args.shape == "large" and not args.no_extra_runs and os.environ.get("MG_BENCH_E1", "1") != "0":
+    if args.full and rank == 0 and world == 1 and args.beams == 1 and args.shape == "large" and not args.no_extra_runs and os.environ.get("MG_BENCH_E1", "1") != "0":
         from markushgrapher_amd.e1 import E1Engine
         from markushgrapher_amd.e1_shapes import PRESETS as E1_PRESETS, recipe_state_dict as e1_recipe
         s1 = E1_PRESETS["swin_b_384"]
@@ -693,7 +722,8 @@ def main():
         del pix_nb
         torch.cuda.empty_cache()
 
-    if rank == 0:
+    roof = phases = single = call_alone_rep = extra = None
+    if args.full and rank == 0:
         H, d, dff, V = shape.num_heads, shape.d_model, shape.d_ff, shape.vocab_size
         n_enc, n_dec, P = shape.num_layers, shape.num_decoder_layers, shape.num_patches
         # attended encoder positions per image (what the path computes on; padding excluded from the algorithmic work)
@@ -702,8 +732,7 @@ def main():
             _, msk = eng.encode(q["input_ids"], q["bbox"], q["attention_mask"], eng.preprocess(q["pages_u8"]))
             xl.append(msk.sum(dim=1).cpu().numpy().astype(np.float64))
         xlen = np.concatenate(xl)
-        absorbed = args.beams == 1 and (eng.cross_absorb is True or (eng.cross_absorb == "auto" and int(round(nb_first)) * B >= eng.ABSORB_AUTO_ROWS))
-        absorbed_main = absorbed
+        absorbed = absorbed_main
         traffic = None if (args.no_pmc or world > 1 or args.beams != 1) else pmc_traffic(args, int(round(nb_first)))
         def make_roof(n_l, ms, keys, empty_ms, with_traffic):
             if n_l.value <= 0:
@@ -987,9 +1016,10 @@ def main():
             # (the VTL calls take two batches of 32 pages each, as the headline run's calls do)
             extra["configs4_end_to_end_1gpu"] = configs4_run(eng, B, new_tokens, ocr_pages=512, ocr_slots=128, main_inflight=4, ocr_inflight=4,
                                                              main_batch=2 * B)
+    if rank == 0:
         out = {
             "metric": METRIC, "value": round(world * B * args.steps / dt, 3), "unit": "images/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2),
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2), "full": bool(args.full),
             # `value` / `ms_per_step` = the median of `repeats` timed regions of exactly `steps` steps each (ms_per_step x steps x repeats of wall clock)
             "repeats": repeats, "value_min": round(world * B * args.steps / max(dts), 3), "value_max": round(world * B * args.steps / min(dts), 3),
             "ms_per_step_all": [round(x / args.steps * 1e3, 2) for x in dts],
@@ -1015,7 +1045,7 @@ def main():
                        "in_flight": "execution contexts on one set of weights (mg_clone), a stream + host thread + workspace each; a call "
                                     "of a context takes `batches_per_call` batches of 32 (rows side by side: one pass over the decoder's "
                                     "weights per step for all of them); every step is one whole batch start to end; ids identical to "
-                                    "one-batch-at-a-time calls (checked in this run: ids_equal_one_batch_calls); warm-up = `warmup` "
+                                    "one-batch-at-a-time calls (checked with --full: ids_equal_one_batch_calls); warm-up = `warmup` "
                                     "calls per context",
                        "parallelism": f"dp{world} (independent image shards; one RCCL all-gather of [32,512] int32 ids + lengths per batch)"},
             # the three readings of "bs = 32 per GPU" side by side at the top level: `value` = 32-image batches packed into calls of
@@ -1031,11 +1061,11 @@ def main():
             "roofline": roof, "phases": phases, "one_call_alone": call_alone_rep, "one_batch_in_flight": single, "with_e1_branch": e1_run,
             "extra_runs": extra,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(shape, sd)
         else:
             out["cpu_baseline"] = None
-        out["setup_s"] = {"recipe_weights": round(t_weights, 1)}
+        out["setup_s"] = {"recipe_weights": round(t_weights, 1), "inputs": round(t_inputs, 1), "warmup": round(t_warmup, 1)}
         try:
             C.CDLL(None).fflush(None)        # RCCL's version banner sits in the C runtime's stdout buffer: out with it BEFORE the result line
         except Exception:

@@ -1,14 +1,15 @@
 #!/bin/bash
-# full check of the tree on the GPU box: GPU tests, default bench -> gpurun_out/<tag>_*   usage: tools/full_check.sh <tag>
+# full check of the tree on the GPU box: GPU tests, `bench.py --full` -> <out>/<tag>_*   usage: tools/full_check.sh <tag> [out, default check_out]
 cd ${GRAFT_REPO_ROOT:-.}
 tag=${1:-check}
-mkdir -p gpurun_out
-timeout 1500 python -m pytest tests -x -q -m gpu 2>&1 | grep -E "passed|failed|error" | tail -3 > gpurun_out/${tag}_gputests.txt
-cat gpurun_out/${tag}_gputests.txt
-timeout 1200 python bench.py > gpurun_out/${tag}_bench_default.json 2> gpurun_out/${tag}_bench_default.err
+out=${2:-check_out}
+mkdir -p $out
+timeout 1500 python -m pytest tests -x -q -m gpu 2>&1 | grep -E "passed|failed|error" | tail -3 > $out/${tag}_gputests.txt
+cat $out/${tag}_gputests.txt
+timeout 1200 python bench.py --full > $out/${tag}_bench_full.json 2> $out/${tag}_bench_full.err
 python - <<PY
 import json
-for l in open("gpurun_out/${tag}_bench_default.json"):
+for l in open("$out/${tag}_bench_full.json"):
     l=l.strip()
     if l.startswith("{"):
         d=json.loads(l); p=d["phases"]; o=d["one_batch_in_flight"]

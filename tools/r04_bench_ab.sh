@@ -5,7 +5,7 @@ out=gpurun_out/r04_bench_ab.txt
 : > $out
 for v in "$@"; do
   for inf in 4 1; do
-    MG_GEMM_VARIANT=$v timeout 600 python bench.py --steps 12 --warmup 2 --no-extra-runs --no-cpu-baseline --no-pmc --inflight $inf 2>/dev/null | python -c "
+    MG_GEMM_VARIANT=$v timeout 600 python bench.py --full --steps 12 --warmup 2 --no-extra-runs --no-cpu-baseline --no-pmc --inflight $inf 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     l=l.strip()
