@@ -388,6 +388,33 @@ int mgk_gemm_pair(void* stream, const void* Wn_pk, const void* Wr_pk, const floa
 int mgk_add_norm_pack(void* stream, float* h, const float* P, int KS, int ldp, size_t slab_stride, const float* gain,
                       void* x_pk, int M, int d, float eps, float scale);
 int mgk_relu_pack(void* stream, const float* P, int KS, int ldp, size_t slab_stride, void* y_pk, int M, int N);
+/* Beam-search step kernels, on buffers the caller owns (device pointers), in the launch order of the decode step.  Geometry: 2 <= K <= 8,
+ * B * K <= 1024, max_len >= 2 (MG_E_SHAPE otherwise; mgk_beam_state_bytes then returns 0).
+ *   init        state (mgk_beam_state_bytes), next_ids [B*K] i64, anc [T_cap][B*K] (T_cap >= max_len - 1), counters [8] i32 ([0] continue)
+ *   step        logits [B*K][ldl] (columns >= V never read); cur_len by value, or tdev (cur_len = *tdev + 1) with div_table [max_len + 1]
+ *               of mgk_beam_length_divisor values; slot_pos / slot_live [B*K] (both or neither): the queue form.  Writes next_ids, beam_idx
+ *               [B*K] i32 and, in the batch form, counters[0]
+ *   reorder_anc anc[j][r] <- anc[j][beam_idx[r]] for j < t_written (tdev: j <= *tdev; queue form: rows of live slots with j <= pos)
+ *   finalize    out_ids [B*num_return][max_len], out_cols [1], out_scores [B*num_return], beam_indices / token_scores
+ *               [B*num_return][max_len - 1] (nullable)
+ *   slots_step  the queue form's end / assign / init after a step: pos, img, pool, live [slots*K], bpool, assign [slots], ctr [16] i32
+ *               ([0] live slots, [1] images done, [2] steps, [4] queue head, [5] images ready, [7] oldest live image), out_ids
+ *               [N*num_return][max_len], out_len [N], out_scores [N*num_return], beam_indices / token_scores as finalize */
+size_t mgk_beam_state_bytes(int B, int K, int max_len);
+float mgk_beam_length_divisor(int cur_len, float length_penalty);
+int mgk_beam_init(void* stream, void* state, int B, int K, int max_len, int pad, int eos, int start, int64_t* next_ids, int* anc, int T_cap,
+                  int* counters);
+int mgk_beam_step(void* stream, void* state, const float* logits, int ldl, int V, int B, int K, int max_len, int cur_len, const int* tdev,
+                  const float* div_table, int eos, int min_len, float length_penalty, int early_stopping, int64_t* next_ids, int* beam_idx,
+                  int* counters, const int* slot_pos, const int* slot_live);
+int mgk_beam_reorder_anc(void* stream, int* anc, const int* beam_idx, int rows, int t_written, const int* tdev, const int* counters,
+                         const int* slot_pos, const int* slot_live);
+int mgk_beam_finalize(void* stream, void* state, int B, int K, int max_len, int64_t* out_ids, int* out_cols, float* out_scores, int num_return,
+                      int* beam_indices, float* token_scores);
+int mgk_beam_slots_step(void* stream, void* state, int slots, int K, int max_len, int pad, int eos, int start, int early_stopping, int* pos,
+                        int* img, int* pool, int* bpool, int* live, int* assign, int64_t* next_ids, int* anc, int T_cap, int pool_cap,
+                        int64_t* out_ids, int* out_len, float* out_scores, int* ctr, int end_first, int num_return, int* beam_indices,
+                        float* token_scores);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
  * ChemicalOCR stage ("next" row f-1).  Replaces, for the OCR pass that produces the cells the main model

@@ -258,6 +258,52 @@ int mgk_greedy_select_fused(void* stream, const void* ptop, const float* stopv, 
     return MG_OK;
 }
 
+// Beam-search step kernels (k_beam.hip) on caller-owned buffers, one launch sequence per call as decode_step (engine.hip) enqueues it.
+// slot_pos / slot_live both null: batch form; both given: queue form (BeamSlots).
+static bool beam_geometry_ok(int B, int K, int max_len) { return B >= 1 && K >= 2 && K <= 8 && B * K <= 1024 && max_len >= 2; }
+size_t mgk_beam_state_bytes(int B, int K, int max_len) { return beam_geometry_ok(B, K, max_len) ? beam_state_bytes(B, K, max_len) : 0; }
+float mgk_beam_length_divisor(int cur_len, float length_penalty) { return beam_length_divisor(cur_len, length_penalty); }
+int mgk_beam_init(void* stream, void* state, int B, int K, int max_len, int pad, int eos, int start, int64_t* next_ids, int* anc, int T_cap,
+                  int* counters) {
+    if (!beam_geometry_ok(B, K, max_len) || T_cap < max_len - 1) return MG_E_SHAPE;
+    beam_init(state, B, K, max_len, pad, eos, start, next_ids, anc, T_cap, counters, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_beam_step(void* stream, void* state, const float* logits, int ldl, int V, int B, int K, int max_len, int cur_len, const int* tdev,
+                  const float* div_table, int eos, int min_len, float length_penalty, int early_stopping, int64_t* next_ids, int* beam_idx,
+                  int* counters, const int* slot_pos, const int* slot_live) {
+    if (!beam_geometry_ok(B, K, max_len) || V < 2 * K || ldl < V || (!slot_pos != !slot_live)) return MG_E_SHAPE;
+    if ((tdev || slot_pos) && !div_table) return MG_E_ARG;
+    const BeamSlots bs{slot_pos, slot_live};
+    beam_step(state, logits, ldl, V, B, K, max_len, cur_len, tdev, div_table, eos, min_len, length_penalty, early_stopping, next_ids, beam_idx,
+              counters, (mgStream_t)stream, slot_pos ? &bs : nullptr);
+    return MG_OK;
+}
+int mgk_beam_reorder_anc(void* stream, int* anc, const int* beam_idx, int rows, int t_written, const int* tdev, const int* counters,
+                         const int* slot_pos, const int* slot_live) {
+    if (rows < 1 || rows > 1024 || t_written < 1 || (!slot_pos != !slot_live)) return MG_E_SHAPE;
+    const BeamSlots bs{slot_pos, slot_live};
+    beam_reorder_anc(anc, beam_idx, rows, t_written, tdev, counters, (mgStream_t)stream, slot_pos ? &bs : nullptr);
+    return MG_OK;
+}
+int mgk_beam_finalize(void* stream, void* state, int B, int K, int max_len, int64_t* out_ids, int* out_cols, float* out_scores, int num_return,
+                      int* beam_indices, float* token_scores) {
+    if (!beam_geometry_ok(B, K, max_len) || num_return < 1 || num_return > K) return MG_E_SHAPE;
+    const BeamOut nb{num_return, beam_indices, token_scores};
+    beam_finalize(state, B, K, max_len, out_ids, out_cols, out_scores, (mgStream_t)stream, &nb);
+    return MG_OK;
+}
+int mgk_beam_slots_step(void* stream, void* state, int slots, int K, int max_len, int pad, int eos, int start, int early_stopping, int* pos,
+                        int* img, int* pool, int* bpool, int* live, int* assign, int64_t* next_ids, int* anc, int T_cap, int pool_cap,
+                        int64_t* out_ids, int* out_len, float* out_scores, int* ctr, int end_first, int num_return, int* beam_indices,
+                        float* token_scores) {
+    if (!beam_geometry_ok(slots, K, max_len) || T_cap < max_len - 1 || pool_cap < 1 || num_return < 1 || num_return > K) return MG_E_SHAPE;
+    const BeamOut nb{num_return, beam_indices, token_scores};
+    beam_slots_step(state, slots, K, max_len, pad, eos, start, early_stopping, pos, img, pool, bpool, live, assign, next_ids, anc, T_cap, pool_cap,
+                    out_ids, out_len, out_scores, ctr, end_first != 0, (mgStream_t)stream, &nb);
+    return MG_OK;
+}
+
 int mgk_gemm_splitk(void* stream, const void* X_pk, const void* W_pk, float* P, int M, int N, int K, int ldp,
                     size_t slab_stride, int KS) {
     if ((K & 63) || KS < 1 || KS > 16 || M > 256) return MG_E_SHAPE;
