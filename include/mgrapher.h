@@ -344,6 +344,22 @@ int mgk_attention_enc_skip(void* stream, const void* Q, const void* K, const voi
                            uint8_t* qbv_scratch);
 int mgk_attention_step(void* stream, const void* q, const void* Kc, const void* Vc, void* ctx_pk, int rows, int H,
                        int group, int cap, const int* len, int n_keys, const float* bias, const int* anc, int t);
+/* mgk_attention_step plus what the engine sets on a decode step: position from device memory (t_dev + t_off) or per row (pos_rows + t_off),
+ * kv_owner (per row for group 1, per group of rows otherwise; indexes len too), live (rows / groups with 0 are not computed or written),
+ * the deferred RMSNorm scale of the query rows as partial sums qrs_part [rows][qrs_nparts] (r = rsqrt(sum * qrs_inv_d + qrs_eps), null: 1),
+ * ctx_pk as columns [ctx_col0, ctx_col0 + H*64) of a packed buffer ctx_ld wide (0: H*64), one_wg_per_cu (cross form, group 1). */
+int mgk_attention_step_ex(void* stream, const void* q, const void* Kc, const void* Vc, void* ctx_pk, int rows, int H, int group, int cap,
+                          const int* len, int n_keys, const float* bias, const int* anc, int t, const int* t_dev, int t_off,
+                          const int* pos_rows, const int* kv_owner, const int* live, const float* qrs_part, int qrs_nparts, float qrs_inv_d,
+                          float qrs_eps, int ctx_ld, int ctx_col0, int one_wg_per_cu);
+/* The rotary grouped-query form of the step (ChemicalOCR text model): qkv fp32 [rows][ld] = [H_kv*group q | H_kv k | H_kv v] x 64, rotated
+ * by cs [positions][cos 32 | sin 32] at the row's position, scaled by the deferred RMSNorm scale rs_* (q also by qscale), rounded to bf16;
+ * k, v appended to Kc / Vc [pages][H_kv][cap][64] at the position, attention over [0, position].  group in {1, 2, 3, 4, 6, 8}
+ * (MG_E_SHAPE otherwise).  Position: pos_rows / t_dev / t as above, plus t_off_rows[page]; page = kv_owner ? kv_owner[row] : row. */
+int mgk_attention_step_rope(void* stream, const float* qkv, int ld, const float* cs, const float* rs_part, int rs_nparts, float rs_inv_d,
+                            float rs_eps, float qscale, void* Kc, void* Vc, void* ctx_pk, int rows, int H_kv, int group, int cap, int t,
+                            const int* t_dev, int t_off, const int* pos_rows, const int* t_off_rows, const int* kv_owner, const int* live,
+                            int ctx_ld, int ctx_col0);
 /* Weight-absorbed cross-attention of one decoder layer and step (mg_set_cross_absorb; kernels of markushgrapher_amd/csrc/k_xattn.hip):
  * ctx[row][h] = softmax(q_h (enc Wk_h^T)^T) (enc Wv_h^T) (stock modeling_udop.py:524-575 without a position bias) evaluated as
  * [softmax((q_h Wk_h) enc^T) enc] Wv_h^T on the states themselves.  q [rows][H][64] bf16; wkv fp32 [2*H*64][d], K rows first;

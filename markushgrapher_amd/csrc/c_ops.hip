@@ -133,6 +133,49 @@ int mgk_attention_step(void* stream, const void* q, const void* Kc, const void* 
     return MG_OK;
 }
 
+// mgk_attention_step with the AttnStepArgs fields the engine sets on every decode step (test entry; nullable pointers = not used, as in
+// AttnStepArgs): the position from device memory (t_dev + t_off) or per row (pos_rows), the K/V pool indirection (kv_owner: per row for
+// group 1, per owner = image slot otherwise), dead rows (live), the deferred RMSNorm scale of the queries (qrs_*), the context as a
+// column window [ctx_col0, ctx_col0 + H*64) of a packed buffer of ctx_ld columns, and the one-workgroup-per-CU residency of the cross form.
+int mgk_attention_step_ex(void* stream, const void* q, const void* Kc, const void* Vc, void* ctx_pk, int rows, int H, int group, int cap,
+                          const int* len, int n_keys, const float* bias, const int* anc, int t, const int* t_dev, int t_off,
+                          const int* pos_rows, const int* kv_owner, const int* live, const float* qrs_part, int qrs_nparts, float qrs_inv_d,
+                          float qrs_eps, int ctx_ld, int ctx_col0, int one_wg_per_cu) {
+    if (group < 1 || group > 8 || rows < 1) return MG_E_SHAPE;
+    if (ctx_ld ? ((ctx_ld & 15) || ctx_col0 < 0 || ctx_col0 + H * 64 > ctx_ld) : ctx_col0 != 0) return MG_E_SHAPE;
+    if (one_wg_per_cu) attention_step_allow_shared();
+    AttnStepArgs a{};
+    a.q = (const uint16_t*)q; a.Kc = (const uint16_t*)Kc; a.Vc = (const uint16_t*)Vc; a.ctx = (uint16_t*)ctx_pk;
+    a.rows = rows; a.H = H; a.group = group; a.cap = cap; a.len = len; a.n_keys = n_keys; a.bias = bias; a.anc = anc;
+    a.t = t; a.t_dev = t_dev; a.t_off = t_off; a.pos_rows = pos_rows; a.kv_owner = kv_owner; a.live = live;
+    a.qrs = RowScale{qrs_part, qrs_nparts, qrs_inv_d, qrs_eps};
+    a.ctx_ld = ctx_ld; a.ctx_col0 = ctx_col0; a.one_wg_per_cu = one_wg_per_cu;
+    attention_step(a, (mgStream_t)stream);
+    return MG_OK;
+}
+
+// The rotary grouped-query form (every layer of the ChemicalOCR text model; test entry): qkv fp32 [rows][ld] = [H_kv*group q heads |
+// H_kv k heads | H_kv v heads] x 64 un-normalised, cs [positions][cos 32 | sin 32], rs_* the deferred RMSNorm scale of the rows
+// (rs_part null: none), Kc / Vc [pages][H_kv][cap][64] bf16 - read over [0, position) and appended to at the position.  Position of a
+// row: pos_rows ? pos_rows[row] + t_off : (t_dev ? *t_dev + t_off : t), plus t_off_rows[page] where given; page = kv_owner ? kv_owner[row]
+// : row.  ctx_pk packed [rows padded to 32][ctx_ld ? ctx_ld : H_kv*group*64], written at columns ctx_col0 on.
+int mgk_attention_step_rope(void* stream, const float* qkv, int ld, const float* cs, const float* rs_part, int rs_nparts, float rs_inv_d,
+                            float rs_eps, float qscale, void* Kc, void* Vc, void* ctx_pk, int rows, int H_kv, int group, int cap, int t,
+                            const int* t_dev, int t_off, const int* pos_rows, const int* t_off_rows, const int* kv_owner, const int* live,
+                            int ctx_ld, int ctx_col0) {
+    if (group < 1 || group > 8 || group == 5 || group == 7 || rows < 1) return MG_E_SHAPE;      // (attention_step has no rotary case for 5 and 7)
+    if (!qkv || !cs || ld < (group + 2) * H_kv * 64 || (ld & 3)) return MG_E_ARG;
+    if (ctx_ld ? ((ctx_ld & 15) || ctx_col0 < 0 || ctx_col0 + H_kv * group * 64 > ctx_ld) : ctx_col0 != 0) return MG_E_SHAPE;
+    AttnStepArgs a{};
+    a.Kc = (const uint16_t*)Kc; a.Vc = (const uint16_t*)Vc; a.Kc_w = (uint16_t*)Kc; a.Vc_w = (uint16_t*)Vc; a.ctx = (uint16_t*)ctx_pk;
+    a.rows = rows; a.H = H_kv; a.group = group; a.cap = cap; a.n_keys = t + 1; a.t = t; a.t_dev = t_dev; a.t_off = t_off;
+    a.pos_rows = pos_rows; a.t_off_rows = t_off_rows; a.kv_owner = kv_owner; a.live = live;
+    a.rope.qkv = qkv; a.rope.ld = ld; a.rope.cs = cs; a.rope.rs = RowScale{rs_part, rs_nparts, rs_inv_d, rs_eps}; a.rope.qscale = qscale;
+    a.ctx_ld = ctx_ld; a.ctx_col0 = ctx_col0;
+    attention_step(a, (mgStream_t)stream);
+    return MG_OK;
+}
+
 #ifdef MG_TOOLS
 int mgk_attention_step_trace(void* stream, const void* q, const void* Kc, const void* Vc, void* ctx_pk, int rows, int H, int cap,
                              const int* len, long long* trace) {

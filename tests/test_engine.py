@@ -557,9 +557,10 @@ def test_forced_decode_capture_matches_teacher_forced_oracle(be_name):
     assert np.array_equal(_np(eng, ids2), g["greedy_ids"])
 
 
+@pytest.mark.parametrize("absorb", [False, True], ids=["kv", "absorbed"])
 @pytest.mark.parametrize("be_name", BACKENDS)
 @pytest.mark.parametrize("ids_kind", ["golden-cycle", "random"])
-def test_long_positions_forced_decode(be_name, ids_kind):
+def test_long_positions_forced_decode(be_name, ids_kind, absorb):
     """Decode positions far beyond the fixtures' 11-16 steps: the KV-cached decode path is teacher-forced
     through 260 (emulator) / 511 (GPU) positions - the bench runs 256, the reference generate(max_length=512) - and every
     step's logits are compared with the oracle's teacher-forced decoder.  The positional bias passes through its exact
@@ -567,7 +568,10 @@ def test_long_positions_forced_decode(be_name, ids_kind):
     Tolerance: the standard logit tolerance for in-distribution ids (the golden sequences, cycled); for random ids the trained
     tiny model is far out of distribution and bf16 storage alone moves its logits by more than that (the fp32 and the
     bf16-emulating oracle differ by ~0.2), so the bound is re-derived per run as 2 x max|oracle_fp32 - oracle_bf16| (never
-    below the standard one).  Argmax must agree wherever the fp32 margin exceeds twice the tolerance."""
+    below the standard one).  Argmax must agree wherever the fp32 margin exceeds twice the tolerance.
+    Both forms of the cross-attention are forced (`auto` would pick the K / V form at these row counts, and the absorbed form would
+    never see 511 positions): the K / V form is held to the standard tolerance on golden ids, the weight-absorbed form to its own
+    measured bound (below)."""
     from oracle.udop_oracle import Oracle
     import torch
     if be_name == "emu" and ids_kind == "random":
@@ -584,6 +588,7 @@ def test_long_positions_forced_decode(be_name, ids_kind):
         forced = np.stack([np.resize(gi[b][gi[b] > 1], T) for b in range(B)])
     forced[:, 0] = shape.decoder_start_token_id
     eng = make_engine(be_name, shape, sd, max_decode_len=512)
+    eng.set_cross_absorb(absorb)
     cap = eng.debug_decode_capture(T - 1, B, forced)
     ids, _, _ = eng.generate(inp["input_ids"], inp["bbox"], inp["attention_mask"], inp["pixel_values"], max_length=T, min_length=T)
     cap, ids = _np(eng, cap).copy().transpose(1, 0, 2), _np(eng, ids).copy()
@@ -599,9 +604,16 @@ def test_long_positions_forced_decode(be_name, ids_kind):
     storage = float(np.abs(ref[False] - ref[True]).max())         # what bf16 storage alone does to these logits (fp32 vs bf16-emulating oracle)
     # random ids: 2 x the storage effect.  Golden ids at 511 positions: the storage effect (0.184 of max |logit| 12.0) is itself within 8 % of
     # the standard tolerance (0.1995), and the HIP path sits right there - measured max 0.1865 with the K / V form of the cross-attention,
-    # 0.2006 with the weight-absorbed form (means 0.00465 / 0.00482; tools/xattn_err_probe.py) - so the bound is at least 1.25 x the storage effect
-    tol = max(tol, (2.0 if ids_kind == "random" else 1.25) * storage)
+    # 0.2006 with the weight-absorbed form (means 0.00465 / 0.00482; tools/xattn_err_probe.py).  The K / V form is inside the standard
+    # tolerance and is held to it; only the absorbed form gets at least 1.25 x the storage effect.  (Emulator, 2 rows x 260 positions, golden
+    # ids: 0.0676 K / V, 0.0605 absorbed against a standard tolerance of 0.1979.)
+    if ids_kind == "random":
+        tol = max(tol, 2.0 * storage)
+    elif absorb:
+        tol = max(tol, 1.25 * storage)
     err = np.abs(cap - ref[False]).max(axis=(0, 2))                # per step
+    print("long positions, %s, %s form: max |logit error| %.4f at step %d, bound %.4f (standard tolerance %.4f, storage effect %.4f)"
+          % (ids_kind, "absorbed" if absorb else "K/V", float(err.max()), int(err.argmax()), tol, logit_tol(ref[False]), storage))
     assert err.max() < tol, (int(err.argmax()), float(err.max()), tol)
     # no drift with position: the late steps are no worse than the early ones (beyond noise)
     assert err[128:].max() < max(1.5 * err[:64].max(), 0.5 * tol)
