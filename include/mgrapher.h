@@ -314,12 +314,15 @@ int mgk_set_pp_parts(int mode);
 int mgk_gemm_resid_mt(void* stream, const void* X_pk, const void* W_pk, float* h, const float* gain, float gscale, void* x_pk,
                       float* part, int M, int N, int K, const float* rs_part, int rs_nparts, float rs_inv_d, float rs_eps, int wide_tiles,
                       float* kpart, int* ticket);
+/* epi: 0 fp32 store (+ bias), 1 fp32 accumulate, 2 / 3 packed relu / packed, 7 packed gelu(tanh) (large-M tile kernels only), and
+ * (mode 0 only, N % 16 == 0) 8 packed bf16(acc + bias[n]), 9 packed bf16(gelu_erf(acc + bias[n])); bias nullable */
 int mgk_gemm(void* stream, int mode, int epi, const void* X_pk, const void* W_pk, int M, int N, int K, float* out_f32,
              int ldo, const float* bias, void* out_pk);
 /* Deferred-RMSNorm pair of the encoder (tiled large-M kernels): epi 5 (EPI_RESID_NORM): h_tiled (fp32, tiles of
  * [32 rows][4 features]: index ((m/32)*(N/4) + n/4)*128 + (m%32)*4 + n%4) += X W^T, out_pk = pack(bf16(h * gain)) un-normalised,
  * part[M][part_ld] = per-64-column partial sums of h^2; epi 3 / 2 (packed / packed relu): rows scaled by
- * rsqrt(sum(rs_part[m][0..rs_nparts)) * rs_inv_d + rs_eps) (rs_part NULL: no scale). */
+ * rsqrt(sum(rs_part[m][0..rs_nparts)) * rs_inv_d + rs_eps) (rs_part NULL: no scale).  M is a multiple of 32, except for epi 5 with gain,
+ * out_pk, part and rs_part all NULL (the plain tiled residual update of the Swin branch: rows >= M are not written). */
 int mgk_gemm_norm(void* stream, int epi, const void* X_pk, const void* W_pk, int M, int N, int K, float* h_tiled, const float* gain,
                   void* out_pk, float* part, int part_ld, const float* rs_part, int rs_nparts, float rs_inv_d, float rs_eps);
 /* mgk_gemm / mgk_gemm_norm restricted to the 32-row tiles that hold a non-zero entry of row_mask [M] (the encoder's row-tile list:
@@ -383,6 +386,29 @@ size_t mgk_embed_meta_bytes(int B, int S_cap);
 int mgk_greedy_select(void* stream, const float* logits, int rows, int V, int ldl, int eos, int pad, int min_len,
                       int64_t* next_ids, int64_t* out_ids, int max_len, int pos, int* unfinished, int* n_unfinished,
                       float* top2);
+
+/* ---- kernels of the OCSR vision branch "e1" (csrc/k_swin.hip; test entries, not on the product path) ---- */
+/* (Shifted-)window attention of one Swin block, head dim 32.  qkv_pk packed bf16 [B*R*R padded to 32][3C] = [q | k | v] in the natural token
+ * order m = (b, y, x) of the R x R map; ctx_pk packed bf16 [B*R*R padded to 32][C] (padding rows are not written); table_HT fp32
+ * [H][(2w-1)^2], entry (dy + w - 1) * (2w - 1) + dx + w - 1 for query - key offsets.  w in {4, 8, 12}, R % w == 0, C == 32 H, H < 4 or
+ * H % 4 == 0 (MG_E_UNSUPPORTED otherwise); 0 <= shift < w. */
+int mgk_swin_attention(void* stream, const void* qkv_pk, void* ctx_pk, const float* table_HT, int B, int R, int C, int H, int w, int shift);
+/* LayerNorm of M rows of C features (biased variance, eps inside the root).  h_in fp32: TILED (in_tiled = 1: tiles of [32 rows][4 features],
+ * the layout of mgk_gemm_norm's h_tiled) or row-major [M][C]; merge_R > 0 (even): h_in is the TILED [B*merge_R^2][C/4] map and row (b, i, j)
+ * of the (merge_R/2)^2 map is [h(2i,2j) | h(2i+1,2j) | h(2i,2j+1) | h(2i+1,2j+1)].  Outputs, each nullable: x_pk packed bf16 [M padded to
+ * 32][kaug ? kaug : C] (kaug > C: column C = 1, the following ones 0); out_f32 row-major [M][C]; h_out TILED [M][C] = the row itself
+ * (h_out_norm = 0) or its normalised form (1), + add_bias [C] (nullable); h_out may be h_in when that is tiled.  C in {64, 128, 256, 512,
+ * 768, 1024, 2048, 4096} (MG_E_UNSUPPORTED otherwise); kaug 0 or a multiple of 16 >= C. */
+int mgk_swin_layernorm(void* stream, const float* h_in, int in_tiled, float* h_out, int h_out_norm, const float* w, const float* b,
+                       const float* add_bias, void* x_pk, float* out_f32, int M, int C, int merge_R, float eps, int kaug);
+/* dst fp32 [B][C][I][I] = bilinear resize (align_corners = false, no antialias) of src fp32 [B][C][S][S], then * scale[c] + shift[c];
+ * scale_host / shift_host: C floats in HOST memory (they travel as kernel arguments).  C <= 4. */
+int mgk_swin_resize(void* stream, const float* src, float* dst, int B, int C, int S, int I, const float* scale_host, const float* shift_host);
+/* pix fp32 [B][C][I][I] -> x_pk packed bf16 [B*(I/ps)^2 padded to 32][Kp], column k = (c*ps + dy)*ps + dx, zero from C*ps*ps on and in the
+ * padding rows.  Kp a multiple of 16 >= C*ps*ps. */
+int mgk_swin_im2col_pack(void* stream, const float* pix, void* x_pk, int B, int C, int I, int ps, int Kp);
+/* src fp32 [n][H] -> dst fp32 [H][n] */
+int mgk_swin_transpose(void* stream, const float* src, float* dst, int n, int H);
 
 /* decode-step split-K projection: P[ks][m*ldp + n] partial sums (ks < KS); consumers sum the slabs */
 int mgk_gemm_splitk(void* stream, const void* X_pk, const void* W_pk, float* P, int M, int N, int K, int ldp,

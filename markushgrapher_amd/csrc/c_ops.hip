@@ -1,6 +1,7 @@
 // C-ABI operator entry points (kernel-level): what the parity tests call to compare each HIP kernel with the
 // oracle.  Plain pointers and sizes only; all pointers are device pointers; work is enqueued on `stream`.
 #include "mg_kernels.h"
+#include "mg_swin.h"
 #include <stdlib.h>
 #include "../../include/mgrapher.h"
 
@@ -33,8 +34,11 @@ int mgk_set_resid_f16(int on) { gemm_rows_set_resid_f16(on); return MG_OK; }
 int mgk_set_rows_ft2(int mode) { gemm_rows_set_ft2(mode); return MG_OK; }
 int mgk_gemm(void* stream, int mode, int epi, const void* X_pk, const void* W_pk, int M, int N, int K, float* out_f32,
              int ldo, const float* bias, void* out_pk) {
-    if ((K & 63) || epi < 0 || (epi > EPI_PK && epi != EPI_PK_GELU)) return MG_E_SHAPE;
+    const bool swin_epi = epi == EPI_PK_BIAS || epi == EPI_PK_GELU_ERF;      // (the Swin branch's: every tile kernel family has them)
+    if ((K & 63) || epi < 0 || (epi > EPI_PK && epi != EPI_PK_GELU && !swin_epi)) return MG_E_SHAPE;
     if (epi == EPI_PK_GELU && !(mode == 0 && gemm_has_gelu_epilogue(M, N))) return MG_E_UNSUPPORTED;
+    if (swin_epi && mode != 0) return MG_E_UNSUPPORTED;
+    if (swin_epi && ((N & 15) || !out_pk)) return MG_E_SHAPE;
     GemmArgs a{};
     a.X = (const uint16_t*)X_pk; a.W = (const uint16_t*)W_pk; a.M = M; a.N = N; a.K = K;
     a.out_f32 = out_f32; a.ldo = ldo; a.bias = bias; a.out_pk = (uint16_t*)out_pk;
@@ -47,7 +51,9 @@ int mgk_gemm(void* stream, int mode, int epi, const void* X_pk, const void* W_pk
 //   epi = EPI_PK / EPI_PK_RELU (3 / 2): out_pk = pack(bf16(relu?(X W^T * r(m)))) with r from rs_part[M][rs_nparts] (null: r = 1)
 int mgk_gemm_norm(void* stream, int epi, const void* X_pk, const void* W_pk, int M, int N, int K, float* h_tiled, const float* gain,
                   void* out_pk, float* part, int part_ld, const float* rs_part, int rs_nparts, float rs_inv_d, float rs_eps) {
-    if ((K & 63) || (N & 31) || (M & 31)) return MG_E_SHAPE;
+    // (a ragged M only in the form the Swin branch issues: the plain tiled residual update without gain / packed output / partial sums)
+    const bool plain_resid = epi == EPI_RESID_NORM && !gain && !out_pk && !part && !rs_part;
+    if ((K & 63) || (N & 31) || ((M & 31) && !plain_resid) || M < 1) return MG_E_SHAPE;
     GemmArgs a{};
     a.X = (const uint16_t*)X_pk; a.W = (const uint16_t*)W_pk; a.M = M; a.N = N; a.K = K;
     a.out_f32 = h_tiled; a.gain = gain; a.out_pk = (uint16_t*)out_pk; a.part = part; a.ldo = part_ld;
@@ -426,6 +432,55 @@ int mgk_relu_pack(void* stream, const float* P, int KS, int ldp, size_t slab_str
     if ((N & 15) || KS < 1 || KS > 16) return MG_E_SHAPE;
     Slabs sl; sl.P = P; sl.KS = KS; sl.ldp = ldp; sl.stride = slab_stride;
     relu_pack(sl, (uint16_t*)y_pk, M, N, (mgStream_t)stream);
+    return MG_OK;
+}
+
+// ---- kernels of the OCSR vision branch (k_swin.hip; test entries) ----
+int mgk_swin_attention(void* stream, const void* qkv_pk, void* ctx_pk, const float* table_HT, int B, int R, int C, int H, int w, int shift) {
+    if (B < 1 || R < 1 || H < 1 || !qkv_pk || !ctx_pk || !table_HT) return MG_E_SHAPE;
+    if (!swin_attention_supported(w, R, C, H)) return MG_E_UNSUPPORTED;
+    if (shift < 0 || shift >= w) return MG_E_SHAPE;
+    SwinAttnArgs a{};
+    a.qkv = (const uint16_t*)qkv_pk; a.ctx = (uint16_t*)ctx_pk; a.table = table_HT;
+    a.B = B; a.R = R; a.C = C; a.H = H; a.w = w; a.shift = shift;
+    swin_attention(a, (mgStream_t)stream);
+    return MG_OK;
+}
+
+int mgk_swin_layernorm(void* stream, const float* h_in, int in_tiled, float* h_out, int h_out_norm, const float* w, const float* b,
+                       const float* add_bias, void* x_pk, float* out_f32, int M, int C, int merge_R, float eps, int kaug) {
+    if (!(swin_ln_supported(C) || C == 768)) return MG_E_UNSUPPORTED;      // (the launcher has no case of its own for any other width)
+    if (M < 1 || !h_in || !w || !b || merge_R < 0 || (merge_R & 1)) return MG_E_SHAPE;
+    if (kaug && ((kaug & 15) || kaug < C)) return MG_E_SHAPE;
+    if (merge_R) {                     // the gather reads the TILED map of width C / 4; whole images; not in place
+        const int P = (merge_R >> 1) * (merge_R >> 1);
+        if (!in_tiled || (C & 15) || M % P || h_out == h_in) return MG_E_SHAPE;
+    }
+    if (h_out == h_in && !in_tiled) return MG_E_SHAPE;
+    SwinLnArgs a{};
+    a.h_in = h_in; a.in_tiled = in_tiled; a.h_out = h_out; a.h_out_norm = h_out_norm; a.w = w; a.b = b; a.add_bias = add_bias;
+    a.x_pk = (uint16_t*)x_pk; a.out_f32 = out_f32; a.M = M; a.C = C; a.merge_R = merge_R; a.eps = eps; a.kaug = kaug;
+    swin_layernorm(a, (mgStream_t)stream);
+    return MG_OK;
+}
+
+int mgk_swin_resize(void* stream, const float* src, float* dst, int B, int C, int S, int I, const float* scale_host, const float* shift_host) {
+    if (B < 1 || C < 1 || C > 4 || S < 1 || I < 1 || !src || !dst || !scale_host || !shift_host) return MG_E_SHAPE;
+    SwinPixAffine af{};
+    for (int c = 0; c < 4; ++c) { af.scale[c] = c < C ? scale_host[c] : 1.0f; af.shift[c] = c < C ? shift_host[c] : 0.0f; }
+    swin_resize(src, dst, B, C, S, I, af, (mgStream_t)stream);
+    return MG_OK;
+}
+
+int mgk_swin_im2col_pack(void* stream, const float* pix, void* x_pk, int B, int C, int I, int ps, int Kp) {
+    if (B < 1 || C < 1 || ps < 1 || I < ps || (I % ps) || (Kp & 15) || Kp < C * ps * ps || !pix || !x_pk) return MG_E_SHAPE;
+    swin_im2col_pack(pix, (uint16_t*)x_pk, B, C, I, ps, Kp, (mgStream_t)stream);
+    return MG_OK;
+}
+
+int mgk_swin_transpose(void* stream, const float* src, float* dst, int n, int H) {
+    if (n < 1 || H < 1 || !src || !dst || src == dst) return MG_E_SHAPE;
+    swin_transpose_f32(src, dst, n, H, (mgStream_t)stream);
     return MG_OK;
 }
 

@@ -93,6 +93,9 @@ PRESETS: Dict[str, E1Shape] = {
     # window 12 at a small size (GPU fixture; the emulator takes minutes on it): 96 px -> 24 x 24 -> 12 x 12
     "w12": E1Shape(image_size=96, embed_dim=64, depths=(2, 2), num_heads=(2, 4), window_size=12, proj_dims=(128,), d_model=64,
                    src_image_size=128),
+    # window 8 (the third window the attention kernel takes, an even tile count): 64 px -> 16 x 16 (shifted windows) -> 8 x 8 (the whole map)
+    "w8": E1Shape(image_size=64, embed_dim=64, depths=(2, 2), num_heads=(2, 4), window_size=8, proj_dims=(128,), d_model=64,
+                  src_image_size=64),
 }
 
 

@@ -47,3 +47,26 @@ def unpack_heads_t(bits, B, H, S_cap):
     t = np.asarray(bits, np.uint16).reshape(B, H, 2, S_cap // 16, 2, 32, 8)   # [b][h][dt][kt][half][dim32][8tok]
     t = t.transpose(0, 1, 3, 4, 6, 2, 5)                                       # [b][h][kt][half][8][dt][dim32]
     return bf16_to_f32(np.ascontiguousarray(t).reshape(B, H, S_cap, 64))
+
+
+def unpack_tile_bits(bits, K):
+    """packed bf16 bits -> the stored bit patterns as uint16 [rows stored][K] (padding rows included)."""
+    Rp = bits.size // K
+    t = np.asarray(bits, np.uint16).reshape(Rp // 32, K // 16, 2, 32, 8).transpose(0, 3, 1, 2, 4)
+    return np.ascontiguousarray(t).reshape(Rp, K)
+
+
+def tile_f32(h, pad_value=0.0):
+    """fp32 H[M][N] -> the tiled residual-stream layout [M/32][N/4][32 rows][4 features] flattened (ht_off in mg_device.h: element
+    (m, n) at ((m // 32) * (N // 4) + n // 4) * 128 + (m % 32) * 4 + n % 4); rows M .. M rounded up to 32 hold pad_value."""
+    M, N = h.shape
+    Mp = (M + 31) // 32 * 32
+    hp = np.full((Mp, N), pad_value, np.float32)
+    hp[:M] = h
+    return np.ascontiguousarray(hp.reshape(Mp // 32, 32, N // 4, 4).transpose(0, 2, 1, 3)).reshape(-1)
+
+
+def untile_f32(t, N):
+    """inverse of tile_f32 -> fp32 [rows stored][N] (padding rows included)."""
+    Mp = t.size // N
+    return np.ascontiguousarray(np.asarray(t, np.float32).reshape(Mp // 32, N // 4, 32, 4).transpose(0, 2, 1, 3)).reshape(Mp, N)

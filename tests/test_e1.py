@@ -226,6 +226,60 @@ def test_e1_odd_batch_rows_do_not_meet(be_name):
     assert np.abs(f3 - fo).max() < EMU_MAX
 
 
+def _stock_features(s, sd, pix):
+    """stock transformers SwinModel (fp32, eager attention) built from the recipe state dict: last_hidden_state"""
+    import torch
+    from transformers import SwinConfig, SwinModel
+    cfg = SwinConfig(image_size=s.image_size, patch_size=s.patch_size, num_channels=s.num_channels, embed_dim=s.embed_dim,
+                     depths=list(s.depths), num_heads=list(s.num_heads), window_size=s.window_size, mlp_ratio=float(s.mlp_ratio),
+                     qkv_bias=True, hidden_act="gelu", layer_norm_eps=s.layer_norm_eps, use_absolute_embeddings=False,
+                     drop_path_rate=0.0)
+    cfg._attn_implementation = "eager"
+    m = SwinModel(cfg, add_pooling_layer=False).eval()
+    m.load_state_dict({k[len("swin."):]: torch.from_numpy(v) for k, v in sd.items() if k.startswith("swin.")}, strict=True)
+    with torch.no_grad():
+        return m(pixel_values=pix).last_hidden_state.numpy()
+
+
+def test_oracle_reproduces_stock_window8():
+    """window 8 has no golden file: stock SwinModel is built here from the recipe weights"""
+    import torch
+    from oracle.swin_oracle import SwinOracle
+    s = PRESETS["w8"]
+    sd = recipe_state_dict(s)
+    orc = SwinOracle(s, sd)
+    with torch.no_grad():
+        pix = orc.derive_input(synth_pixels(s, 2))
+        f = orc.features(pix).numpy()
+    ref = _stock_features(s, sd, pix)
+    assert f.shape == ref.shape == (2, s.out_tokens, s.out_dim)
+    assert np.abs(f - ref).max() < 2e-4
+
+
+@pytest.mark.parametrize("be_name", BACKENDS)
+def test_e1_window8_against_stock_and_oracle(be_name):
+    """window 8 (swin_attn_kernel<4>: an even tile count, no zero-padded key tail) end to end: a 16 x 16 stage with shifted windows and
+    an 8 x 8 stage whose window is the whole map, against the bf16-emulating oracle and, in the CPU tier, stock SwinModel."""
+    import torch
+    from oracle.swin_oracle import SwinOracle
+    s = PRESETS["w8"]
+    sd = recipe_state_dict(s)
+    B = 2
+    src = synth_pixels(s, B)
+    e1, f = make_e1(be_name, s, sd).encode(src, want_features=True)
+    e1, f = _np(e1), _np(f)
+    assert f.shape == (B, s.out_tokens, s.out_dim) and e1.shape == (B, s.out_tokens, s.d_model)
+    emu = SwinOracle(s, sd, emulate_bf16=True)
+    with torch.no_grad():
+        pix = emu.derive_input(src)
+        fe = emu.features(pix).numpy()
+    if be_name == "emu":             # (the CPU tier: stock transformers is built there)
+        err = np.abs(f - _stock_features(s, sd, pix))
+        assert err.max() < FEAT_MAX and err.mean() < FEAT_MEAN, (err.max(), err.mean())
+    assert np.abs(f - fe).max() < EMU_MAX, np.abs(f - fe).max()
+    assert len({f[0, t].tobytes() for t in range(s.out_tokens)}) == s.out_tokens
+
+
 @pytest.mark.gpu
 def test_e1_window12_against_stock():
     g = load_golden("swin_w12.npz")
