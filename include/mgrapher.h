@@ -410,6 +410,63 @@ int mgk_swin_im2col_pack(void* stream, const float* pix, void* x_pk, int B, int 
 /* src fp32 [n][H] -> dst fp32 [H][n] */
 int mgk_swin_transpose(void* stream, const float* src, float* dst, int n, int H);
 
+/* ---- kernels of the ChemicalOCR stage (csrc/k_ocr.hip and the decode-step kernels it starts from; test entries, not on the product path) ----
+ * "packed" = the bf16 fragment-tile format of mgk_gemm's operands, rows padded to 32 (rows >= M are not written unless stated); "tiled" = the
+ * fp32 layout of mgk_gemm_norm's h_tiled.  Each entry returns MG_E_SHAPE / MG_E_UNSUPPORTED for what its launcher assumes without checking.
+ * x_pk packed [M][Kaug] = bf16(LayerNorm(h[m]) * w + b) | 1 at column d | 0 (Kaug a multiple of 16 >= d); out_f32 [M][d] row-major the same
+ * unrounded; h [M][d] row-major += add_bias afterwards.  x_pk, out_f32, add_bias each nullable. */
+int mgk_ocr_layernorm_pack(void* stream, float* h, const float* w, const float* b, const float* add_bias, void* x_pk, float* out_f32, int M,
+                           int d, int Kaug, float eps);
+/* y_pk packed [M][Kaug] = bf16(gelu_tanh(in [M][N])) | 1 at column N | 0 */
+int mgk_ocr_gelu_pack(void* stream, const float* in, void* y_pk, int M, int N, int Kaug);
+/* y_pk packed [M][I] = bf16(silu(in[m][2c]) * in[m][2c + 1]), in [M][2I] gate / up interleaved; _rows: gate and up first multiplied by the row's
+ * deferred RMSNorm scale r = rsqrt(sum(rs_part[m][0..rs_nparts)) * rs_inv_d + rs_eps) (rs_part NULL: 1).  I % 16 == 0. */
+int mgk_ocr_silu_mul_pack(void* stream, const float* in, void* y_pk, int M, int I);
+int mgk_ocr_silu_mul_rows(void* stream, const float* in, const float* rs_part, int rs_nparts, float rs_inv_d, float rs_eps, void* y_pk, int M,
+                          int I);
+/* hidden [N][P_cap][d] = patch [N][P][d] + pos [.][d] (bf16) at row pos_ids [N][P] (NULL: p); rows p >= P zero.  vmask [N][P_cap] (nullable) =
+ * patch_mask [N][P] != 0 (NULL: 1), 0 from P on. */
+int mgk_ocr_add_pos(void* stream, const float* patch, const void* pos, const int* pos_ids, const uint8_t* patch_mask, uint8_t* vmask,
+                    float* hidden, int N, int P, int P_cap, int d);
+/* Idefics3Connector.pixel_shuffle: x_pk packed [N*(g/sf)^2][e*sf*sf], token (n, y2, x2), feature (dy*sf + dx)*e + c <- vis [N][P_cap][e] at
+ * patch (y2*sf + dy)*g + x2*sf + dx.  g % sf == 0, P_cap >= g*g, e*sf*sf % 16 == 0. */
+int mgk_ocr_pixel_shuffle_pack(void* stream, const float* vis, void* x_pk, int N, int g, int P_cap, int e, int sf);
+/* inputs_merger: h [B][T_cap][d] = ids [B][L] == image_token ? feats [B][per_seq][d] (the sequence's k-th <image> takes its row k) : tok_emb
+ * [V][d] (bf16); rows t >= L zero; feats NULL: token embeddings only.  *err += ids outside [0, V) (they read row 0) + sequences whose <image>
+ * count is not per_seq.  L <= 2048 (MG_E_UNSUPPORTED beyond). */
+int mgk_ocr_merge_embed(void* stream, const int64_t* ids, const void* tok_emb, const float* feats, float* h, int B, int L, int T_cap, int d,
+                        int V, int image_token, int per_seq, int* err);
+/* Prefill rotary embedding + head layouts: qkv fp32 [B*T_cap][(H + 2 KV)*64] = [q | k | v]; Q (x 1/8), K rotated at position t = row % T_cap,
+ * bf16, as mgk_attention's operands Q, K [B][H][T_cap][64] (HF_PK_ROWS) and Vt (HF_PK_T) with key/value head hh / (H / KV) repeated for every
+ * query head hh, rows t >= T zero; and once per key/value head into Kc, Vc [B][KV][cap][64], rows t < T only.  H % KV == 0 (MG_E_UNSUPPORTED
+ * otherwise), T <= T_cap, T_cap % 32 == 0, T <= cap. */
+int mgk_ocr_rope_heads(void* stream, const float* qkv, int B, int T, int T_cap, int H, int KV, float theta, void* Q, void* K, void* Vt, void* Kc,
+                       void* Vc, int cap);
+/* cs [positions][cos 32 | sin 32] of angle p * theta^(-i/32): the table mgk_attention_step_rope reads */
+int mgk_ocr_rope_table(void* stream, float* cs, int positions, float theta);
+/* packed weight rows row0 + r*rstride (r < Nfill) of a [.][Kaug] operand <- W [N][K] * scale | bias[r] * scale at column K | 0; rows r >= N zero */
+int mgk_ocr_pack_aug(void* stream, const float* W, const float* bias, float scale, void* dst_pk, int row0, int N, int K, int Kaug, int Nfill,
+                     int rstride);
+/* row-major fp32 [M][d] -> tiled (to_tiled != 0) or back; M % 32 == 0, d % 4 == 0 */
+int mgk_ocr_tile_f32(void* stream, const float* src, float* dst, int M, int d, int to_tiled);
+/* [B][T_cap] each: last_rows = b at t == (lens ? lens[b] : T) - 1 else -1; all_rows = b*T + t for t < T else -1; key_mask = t < (lens ? lens[b] : T) */
+int mgk_ocr_row_maps(void* stream, int* last_rows, int* all_rows, uint8_t* key_mask, int B, int T, int T_cap, const int* lens);
+/* delta[n] = clamp(lens[n], 1, L) - L; *err += lengths outside [1, L] */
+int mgk_ocr_len_delta(void* stream, const int* lens, int* delta, int N, int L, int* err);
+/* The gate / up projection of the decode step (row-streaming kernels, epilogue 6): W_pk packed [N][K], rows gate_0, up_0, gate_1, ...;
+ * out[m][j] = bf16(silu(r acc[m][2j]) * (r acc[m][2j + 1])), r as in mgk_ocr_silu_mul_rows, written as columns [out_col0, out_col0 + N/2) of a
+ * packed buffer out_ld wide (out_ld = 0: N/2 wide, N % 32 == 0).  X_pk: k-tiles [x_k0, x_k0 + K/16) of a packed buffer of x_kts k-tiles per
+ * row tile (x_kts = 0: K/16).  M <= 256 (MG_E_UNSUPPORTED beyond), N % 16 == 0, K % 64 == 0, out_col0 % 4 == 0,
+ * rs_nparts % 8 == 0. */
+int mgk_gemm_swiglu(void* stream, const void* X_pk, int x_kts, int x_k0, const void* W_pk, int M, int N, int K, const float* rs_part,
+                    int rs_nparts, float rs_inv_d, float rs_eps, void* out_pk, int out_ld, int out_col0);
+/* mgk_rmsnorm_pack (scale 1) from the tiled fp32 layout; M % 32 == 0, d % 16 == 0 */
+int mgk_rmsnorm_pack_tiled(void* stream, const float* h_tiled, const float* gain, void* x_pk, float* out_f32, int M, int d, float eps);
+/* h [rows][d] = tok_emb [V][d] (bf16) at ids[row], x_pk packed [rows][d] = bf16(RMSNorm(h) * gain), x2_pk (nullable) columns [x2_col0,
+ * x2_col0 + d) of a packed buffer x2_ld wide = the embedding row itself; an id outside [0, V) adds one to *err and reads row 0 */
+int mgk_embed_norm_rows(void* stream, const int64_t* ids, const void* tok_emb, float* h, const float* gain, void* x_pk, void* x2_pk, int x2_ld,
+                        int x2_col0, int rows, int d, int V, int* err, float eps);
+
 /* decode-step split-K projection: P[ks][m*ldp + n] partial sums (ks < KS); consumers sum the slabs */
 int mgk_gemm_splitk(void* stream, const void* X_pk, const void* W_pk, float* P, int M, int N, int K, int ldp,
                     size_t slab_stride, int KS);

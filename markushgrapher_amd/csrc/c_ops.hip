@@ -2,6 +2,7 @@
 // oracle.  Plain pointers and sizes only; all pointers are device pointers; work is enqueued on `stream`.
 #include "mg_kernels.h"
 #include "mg_swin.h"
+#include "mg_ocr.h"
 #include <stdlib.h>
 #include "../../include/mgrapher.h"
 
@@ -481,6 +482,116 @@ int mgk_swin_im2col_pack(void* stream, const float* pix, void* x_pk, int B, int 
 int mgk_swin_transpose(void* stream, const float* src, float* dst, int n, int H) {
     if (n < 1 || H < 1 || !src || !dst || src == dst) return MG_E_SHAPE;
     swin_transpose_f32(src, dst, n, H, (mgStream_t)stream);
+    return MG_OK;
+}
+
+// ---- kernels of the ChemicalOCR stage (k_ocr.hip and the decode-step kernels it starts from; test entries) ----
+// The launchers check nothing: what each assumes about its arguments is refused here.
+int mgk_ocr_layernorm_pack(void* stream, float* h, const float* w, const float* b, const float* add_bias, void* x_pk, float* out_f32, int M,
+                           int d, int Kaug, float eps) {
+    if (M < 1 || d < 1 || !h || !w || !b || (!x_pk && !out_f32 && !add_bias)) return MG_E_SHAPE;
+    if (Kaug < d || (x_pk && (Kaug & 15))) return MG_E_SHAPE;
+    ocr_layernorm_pack(h, w, b, add_bias, (uint16_t*)x_pk, out_f32, M, d, Kaug, eps, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_ocr_gelu_pack(void* stream, const float* in, void* y_pk, int M, int N, int Kaug) {
+    if (M < 1 || N < 1 || !in || !y_pk || (Kaug & 15) || Kaug < N) return MG_E_SHAPE;
+    ocr_gelu_pack(in, (uint16_t*)y_pk, M, N, Kaug, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_ocr_silu_mul_pack(void* stream, const float* in, void* y_pk, int M, int I) {
+    if (M < 1 || I < 16 || (I & 15) || !in || !y_pk) return MG_E_SHAPE;
+    ocr_silu_mul_pack(in, (uint16_t*)y_pk, M, I, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_ocr_silu_mul_rows(void* stream, const float* in, const float* rs_part, int rs_nparts, float rs_inv_d, float rs_eps, void* y_pk, int M,
+                          int I) {
+    if (M < 1 || I < 16 || (I & 15) || !in || !y_pk || (rs_part && rs_nparts < 1)) return MG_E_SHAPE;
+    ocr_silu_mul_rows(in, RowScale{rs_part, rs_nparts, rs_inv_d, rs_eps}, (uint16_t*)y_pk, M, I, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_ocr_add_pos(void* stream, const float* patch, const void* pos, const int* pos_ids, const uint8_t* patch_mask, uint8_t* vmask,
+                    float* hidden, int N, int P, int P_cap, int d) {
+    if (N < 1 || P < 1 || P > P_cap || d < 1 || !patch || !pos || !hidden) return MG_E_SHAPE;
+    ocr_add_pos(patch, (const uint16_t*)pos, pos_ids, patch_mask, vmask, hidden, N, P, P_cap, d, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_ocr_pixel_shuffle_pack(void* stream, const float* vis, void* x_pk, int N, int g, int P_cap, int e, int sf) {
+    if (N < 1 || sf < 1 || g < sf || (g % sf) || e < 1 || !vis || !x_pk) return MG_E_SHAPE;
+    if (P_cap < g * g || ((e * sf * sf) & 15)) return MG_E_SHAPE;
+    ocr_pixel_shuffle_pack(vis, (uint16_t*)x_pk, N, g, P_cap, e, sf, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_ocr_merge_embed(void* stream, const int64_t* ids, const void* tok_emb, const float* feats, float* h, int B, int L, int T_cap, int d,
+                        int V, int image_token, int per_seq, int* err) {
+    if (B < 1 || L < 1 || T_cap < L || d < 1 || V < 1 || per_seq < 0 || !ids || !tok_emb || !h || !err) return MG_E_SHAPE;
+    if (L > 2048) return MG_E_UNSUPPORTED;       // the kernel's rank table
+    ocr_merge_embed(ids, (const uint16_t*)tok_emb, feats, h, B, L, T_cap, d, V, image_token, per_seq, err, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_ocr_rope_heads(void* stream, const float* qkv, int B, int T, int T_cap, int H, int KV, float theta, void* Q, void* K, void* Vt, void* Kc,
+                       void* Vc, int cap) {
+    if (B < 1 || T < 1 || T > T_cap || (T_cap & 31) || H < 1 || KV < 1 || cap < T || !(theta > 0.f)) return MG_E_SHAPE;
+    if (!qkv || !Q || !K || !Vt || !Kc || !Vc) return MG_E_SHAPE;
+    if (H % KV) return MG_E_UNSUPPORTED;         // whole groups of query heads per key/value head
+    ocr_rope_heads(qkv, B, T, T_cap, H, KV, theta, (uint16_t*)Q, (uint16_t*)K, (uint16_t*)Vt, (uint16_t*)Kc, (uint16_t*)Vc, cap, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_ocr_rope_table(void* stream, float* cs, int positions, float theta) {
+    if (positions < 1 || !cs || !(theta > 0.f)) return MG_E_SHAPE;
+    ocr_rope_table(cs, positions, theta, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_ocr_pack_aug(void* stream, const float* W, const float* bias, float scale, void* dst_pk, int row0, int N, int K, int Kaug, int Nfill,
+                     int rstride) {
+    if (N < 1 || K < 1 || Nfill < N || row0 < 0 || rstride < 1 || !W || !dst_pk) return MG_E_SHAPE;
+    if ((Kaug & 15) || Kaug < K + (bias ? 1 : 0)) return MG_E_SHAPE;
+    ocr_pack_aug(W, bias, scale, (uint16_t*)dst_pk, row0, N, K, Kaug, Nfill, rstride, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_ocr_tile_f32(void* stream, const float* src, float* dst, int M, int d, int to_tiled) {
+    if (M < 32 || (M & 31) || d < 4 || (d & 3) || !src || !dst || src == dst) return MG_E_SHAPE;
+    ocr_tile_f32(src, dst, M, d, to_tiled, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_ocr_row_maps(void* stream, int* last_rows, int* all_rows, uint8_t* key_mask, int B, int T, int T_cap, const int* lens) {
+    if (B < 1 || T < 1 || T > T_cap || !last_rows || !all_rows || !key_mask) return MG_E_SHAPE;
+    ocr_row_maps(last_rows, all_rows, key_mask, B, T, T_cap, (mgStream_t)stream, lens);
+    return MG_OK;
+}
+int mgk_ocr_len_delta(void* stream, const int* lens, int* delta, int N, int L, int* err) {
+    if (N < 1 || L < 1 || !lens || !delta || !err) return MG_E_SHAPE;
+    ocr_len_delta(lens, delta, N, L, err, (mgStream_t)stream);
+    return MG_OK;
+}
+// The gate / up projection of the ChemicalOCR decode step: gemm_rows with EPI_PK_SWIGLU.  W_pk packed [N padded to 32][K], rows gate_0, up_0,
+// gate_1, ...; X_pk a packed buffer of x_kts 16-wide k-tiles per row tile read from k-tile x_k0 on (x_kts = 0: K / 16 and x_k0 = 0); the row
+// scale as in mgk_gemm_norm; out_pk packed [M padded to 32][out_ld], written at columns [out_col0, out_col0 + N / 2) (out_ld = 0: N / 2 wide)
+int mgk_gemm_swiglu(void* stream, const void* X_pk, int x_kts, int x_k0, const void* W_pk, int M, int N, int K, const float* rs_part,
+                    int rs_nparts, float rs_inv_d, float rs_eps, void* out_pk, int out_ld, int out_col0) {
+    if (!X_pk || !W_pk || !out_pk || K < 64 || (K & 63) || N < 16 || (N & 15) || M < 1) return MG_E_SHAPE;
+    if (M > 256) return MG_E_UNSUPPORTED;        // 8 row tiles: beyond them gemm_rows hands over to the tiled kernel, which has no such epilogue
+    if (x_kts ? (x_k0 < 0 || x_k0 + (K >> 4) > x_kts) : x_k0 != 0) return MG_E_SHAPE;
+    if (out_ld ? ((out_ld & 15) || out_col0 < 0 || (out_col0 & 3) || out_col0 + (N >> 1) > out_ld) : (out_col0 != 0 || (N & 31))) return MG_E_SHAPE;
+    if (rs_part && (rs_nparts < 8 || (rs_nparts & 7))) return MG_E_SHAPE;      // (8 threads of the kernel share a row's partial sums)
+    GemmArgs a{};
+    a.X = (const uint16_t*)X_pk; a.x_kts = x_kts; a.x_k0 = x_k0; a.W = (const uint16_t*)W_pk; a.M = M; a.N = N; a.K = K;
+    a.rs = RowScale{rs_part, rs_nparts, rs_inv_d, rs_eps};
+    a.out_pk = (uint16_t*)out_pk; a.out_ld = out_ld; a.out_col0 = out_col0;
+    gemm_rows(a, EPI_PK_SWIGLU, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_rmsnorm_pack_tiled(void* stream, const float* h_tiled, const float* gain, void* x_pk, float* out_f32, int M, int d, float eps) {
+    if (M < 32 || (M & 31) || d < 16 || (d & 15) || !h_tiled || !gain || (!x_pk && !out_f32)) return MG_E_SHAPE;
+    rmsnorm_pack_tiled(h_tiled, gain, (uint16_t*)x_pk, out_f32, M, d, eps, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_embed_norm_rows(void* stream, const int64_t* ids, const void* tok_emb, float* h, const float* gain, void* x_pk, void* x2_pk, int x2_ld,
+                        int x2_col0, int rows, int d, int V, int* err, float eps) {
+    if (rows < 1 || d < 16 || (d & 15) || V < 1 || !ids || !tok_emb || !h || !gain || !x_pk || !err) return MG_E_SHAPE;
+    if (x2_pk && ((x2_ld & 15) || x2_col0 < 0 || (x2_col0 & 7) || x2_col0 + d > x2_ld)) return MG_E_SHAPE;
+    embed_norm_rows(ids, (const uint16_t*)tok_emb, h, gain, (uint16_t*)x_pk, (uint16_t*)x2_pk, x2_ld, x2_col0, rows, d, V, err, eps,
+                    (mgStream_t)stream);
     return MG_OK;
 }
 
