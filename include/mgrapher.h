@@ -484,6 +484,52 @@ int mgk_gemm_resid(void* stream, const void* X_pk, const void* W_pk, float* h, c
  *               out2_pk = pack(relu?(W2 * [hb ; ctx]))     with xwin_pk = packed [rows][d+inner] = [bf16(h_old) | ctx]. */
 int mgk_gemm_pair(void* stream, const void* Wn_pk, const void* Wr_pk, const float* gain, int N2, int d, int inner, void* W2_pk,
                   float* scratch_f32, const void* xwin_pk, float* h, void* hb_out_pk, float* part, void* out2_pk, int M, int relu);
+/* The projections of the decode step as decode_step (engine.hip) sets them up, on operands the caller makes (test entries; every launcher of
+ * this family takes at most 256 rows = 8 row tiles: MG_E_SHAPE beyond, as for K % 64, N % 32 of a residual projection, a window outside
+ * its buffer, a row scale whose partial count is not a multiple of 8).  Packed operands hold their rows padded to 32.
+ * mgk_resid_desc = ResidArgs: X a window of k-tiles [x_k0, x_k0 + K / 16) of a packed buffer x_kts k-tiles wide (x_kts = 0: K / 16, 0);
+ * h [M][N] fp32 += r(m) X W^T; x_pk = bf16(h gain gscale) at columns [x_col0, x_col0 + N) of a packed buffer x_ld wide (x_ld = 0: N), needs
+ * gain; x2_pk = bf16(h) likewise; part [M][N / 8] (required); rs_* the deferred RMSNorm scale of the rows of X (rs_part null: none);
+ * wide_tiles / alone / kpart / ticket as mgk_gemm_resid_mt. */
+typedef struct mgk_resid_desc {
+    const void* X; int x_kts, x_k0;
+    const void* W;
+    float* h;
+    const float* gain; float gscale;
+    void* x_pk; int x_ld, x_col0;
+    void* x2_pk; int x2_ld, x2_col0;
+    float* part;
+    int M, N, K;
+    const float* rs_part; int rs_nparts; float rs_inv_d, rs_eps;
+    int wide_tiles, alone;
+    float* kpart; int* ticket;
+} mgk_resid_desc;
+/* mgk_proj_desc = the second projection of a pair (GemmArgs): its own window of X, W [N padded to 32][K], the row scale, both_halves; the
+ * output by epilogue: 4 (per head) q [M][N / 64][64] bf16 (N = H * 64: target 0 HF_STEP_Q, the others none, as the engine), 2 (packed relu)
+ * out_pk packed [M][N], 0 (fp32 store) out_f32 [M][ldo]. */
+typedef struct mgk_proj_desc {
+    const void* X; int x_kts, x_k0;
+    const void* W;
+    int N, K;
+    const float* rs_part; int rs_nparts; float rs_inv_d, rs_eps;
+    int both_halves;
+    void* q;
+    void* out_pk;
+    float* out_f32; int ldo;
+} mgk_proj_desc;
+int mgk_gemm_resid_ex(void* stream, const mgk_resid_desc* r);
+int mgk_gemm_pair_ex(void* stream, const mgk_resid_desc* r, const mgk_proj_desc* g, int epi);
+/* The QKV launch of the decode step (gemm_rows, per-head epilogue): targets / formats as mgk_gemm_heads (0 none, 4 step q [M][H][64], 5 step
+ * k / v into the cache [M][H][S_cap][64] at the row's position = pos_rows ? pos_rows[m] : (pos_dev ? *pos_dev : pos)), X as a window, the
+ * deferred row scale, GemmArgs::both_halves. */
+int mgk_gemm_heads_step(void* stream, const void* X_pk, int x_kts, int x_k0, const void* W_pk, int M, int N, int K, void* p0, void* p1, void* p2,
+                        int f0, int f1, int f2, int H, int S_cap, const float* rs_part, int rs_nparts, float rs_inv_d, float rs_eps, int pos,
+                        const int* pos_dev, const int* pos_rows, int both_halves);
+/* The lm_head launch of the decode step (gemm_rows_splitk, KS = 1) with the row scale; ptop null: plain projection into P [M][ldp]; otherwise
+ * the greedy tail's partials ptop [M][ceil(N / 32)] float4 = {best, second, index of the best (int bits), lse ? sum exp(x - best) : 0} over each
+ * 32-feature tile's non-stop features, stopv [M][4] = the logits of stop[0 .. 3] (-1: unused), P written only with write_logits. */
+int mgk_lm_head_step(void* stream, const void* X_pk, const void* W_pk, float* P, int M, int N, int K, int ldp, const float* rs_part, int rs_nparts,
+                     float rs_inv_d, float rs_eps, void* ptop, float* stopv, const int* stop4_host, int write_logits, int lse);
 int mgk_add_norm_pack(void* stream, float* h, const float* P, int KS, int ldp, size_t slab_stride, const float* gain,
                       void* x_pk, int M, int d, float eps, float scale);
 int mgk_relu_pack(void* stream, const float* P, int KS, int ldp, size_t slab_stride, void* y_pk, int M, int N);

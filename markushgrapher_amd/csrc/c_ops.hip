@@ -93,6 +93,33 @@ int mgk_gemm_heads(void* stream, int mode, const void* X_pk, const void* W_pk, i
     return MG_OK;
 }
 
+int mgk_gemm_heads_step(void* stream, const void* X_pk, int x_kts, int x_k0, const void* W_pk, int M, int N, int K, void* p0, void* p1, void* p2,
+                        int f0, int f1, int f2, int H, int S_cap, const float* rs_part, int rs_nparts, float rs_inv_d, float rs_eps, int pos,
+                        const int* pos_dev, const int* pos_rows, int both_halves) {
+    if (!X_pk || !W_pk) return MG_E_ARG;
+    if (K < 64 || (K & 63) || H < 1 || N < H * 64 || (N % (H * 64)) || N > 3 * H * 64 || M < 1 || M > 256 || S_cap < 1) return MG_E_SHAPE;
+    if (x_kts ? (x_k0 < 0 || x_k0 + (K >> 4) > x_kts) : x_k0 != 0) return MG_E_SHAPE;
+    if (rs_part && (rs_nparts < 8 || (rs_nparts & 7))) return MG_E_SHAPE;
+    void* const ptr[3] = {p0, p1, p2};
+    const int fmt[3] = {f0, f1, f2};
+    bool kv = false;
+    for (int i = 0; i < 3; ++i) {
+        if (fmt[i] != HF_NONE && fmt[i] != HF_STEP_Q && fmt[i] != HF_STEP_KV) return MG_E_UNSUPPORTED;
+        if (i < N / (H * 64) && fmt[i] != HF_NONE && !ptr[i]) return MG_E_ARG;
+        kv = kv || fmt[i] == HF_STEP_KV;
+    }
+    if (kv && !pos_dev && !pos_rows && (pos < 0 || pos >= S_cap)) return MG_E_SHAPE;
+    GemmArgs a{};
+    a.X = (const uint16_t*)X_pk; a.x_kts = x_kts; a.x_k0 = x_k0; a.W = (const uint16_t*)W_pk; a.M = M; a.N = N; a.K = K;
+    for (int i = 0; i < 3; ++i) { a.heads.ptr[i] = (uint16_t*)ptr[i]; a.heads.fmt[i] = fmt[i]; }
+    a.heads.inner = H * 64; a.heads.H = H; a.heads.S_in = M; a.heads.S_cap = S_cap;
+    a.heads.pos = pos; a.heads.pos_dev = pos_dev; a.heads.pos_rows = pos_rows;
+    a.rs = RowScale{rs_part, rs_nparts, rs_inv_d, rs_eps};
+    a.both_halves = both_halves;
+    gemm_rows(a, EPI_HEADS, (mgStream_t)stream);
+    return MG_OK;
+}
+
 int mgk_attention(void* stream, int mode, const void* Q, const void* K, const void* Vt, void* ctx_pk, int B, int H,
                   int Sq, int Sk, int Sq_cap, int Sk_cap, const uint8_t* kmask, const float* tab1, int tab1_len,
                   const float* tabh, const float* tabv, const double* cx, const double* cy, const int* bk1, const int* bkhv,
@@ -291,6 +318,26 @@ int mgk_lm_head_top(void* stream, const void* X_pk, const void* W_pk, float* P, 
     return MG_OK;
 }
 
+// mgk_lm_head_top as the decode step launches it: the deferred row scale of the final norm and up to four stop tokens (host array, -1 = unused);
+// ptop null: the plain projection (the unfused tail's launch)
+int mgk_lm_head_step(void* stream, const void* X_pk, const void* W_pk, float* P, int M, int N, int K, int ldp, const float* rs_part, int rs_nparts,
+                     float rs_inv_d, float rs_eps, void* ptop, float* stopv, const int* stop4_host, int write_logits, int lse) {
+    if (!X_pk || !W_pk) return MG_E_ARG;
+    if (K < 64 || (K & 63) || M > 256 || M < 1 || N < 1) return MG_E_SHAPE;
+    if (rs_part && (rs_nparts < 8 || (rs_nparts & 7))) return MG_E_SHAPE;
+    const bool writes = !ptop || write_logits;
+    if (writes && (!P || ldp < N)) return MG_E_ARG;
+    if (ptop && (!stopv || !stop4_host)) return MG_E_ARG;
+    const RowScale rs{rs_part, rs_nparts, rs_inv_d, rs_eps};
+    if (!ptop) {
+        gemm_rows_splitk((const uint16_t*)X_pk, (const uint16_t*)W_pk, P, M, N, K, ldp, 0, 1, rs, (mgStream_t)stream);
+        return MG_OK;
+    }
+    TopOut top{(float4*)ptop, stopv, {stop4_host[0], stop4_host[1], stop4_host[2], stop4_host[3]}, write_logits ? 1 : 0, lse ? 1 : 0};
+    gemm_rows_splitk((const uint16_t*)X_pk, (const uint16_t*)W_pk, P, M, N, K, ldp, 0, 1, rs, (mgStream_t)stream, &top);
+    return MG_OK;
+}
+
 // greedy_select_fused on lm_head partials (mgk_lm_head_top): selection, bookkeeping, optional token scores, and the next step's embedding
 // + first RMSNorm of the selected token (tok_emb [V][d] bf16, gain [d], h [rows][d] fp32, x_pk packed bf16 [rows padded to 32][d])
 int mgk_greedy_select_fused(void* stream, const void* ptop, const float* stopv, int rows, int V, int eos, int pad, int min_len,
@@ -364,14 +411,57 @@ int mgk_gemm_splitk(void* stream, const void* X_pk, const void* W_pk, float* P, 
 int mgk_splitk_factor(int N, int K) { return splitk_factor(N, K); }
 int mgk_gemm_set_variant(int v) { gemm_set_variant(v); return MG_OK; }
 
-int mgk_gemm_resid(void* stream, const void* X_pk, const void* W_pk, float* h, const float* gain, float gscale, void* x_pk,
-                   float* part, int M, int N, int K, const float* rs_part, int rs_nparts, float rs_inv_d, float rs_eps) {
-    if ((K & 63) || (N & 31) || M > 256) return MG_E_SHAPE;
+// true when a row scale / a column window / a k-tile window is one the decode-step kernels can take
+static bool rs_ok(const float* part, int nparts) { return !part || (nparts >= 8 && (nparts & 7) == 0); }      // (8 threads share a row's partial sums)
+static bool kwin_ok(int x_kts, int x_k0, int K) { return x_kts ? (x_k0 >= 0 && x_k0 + (K >> 4) <= x_kts) : x_k0 == 0; }
+static bool cwin_ok(int ld, int col0, int N) { return ld ? ((ld & 15) == 0 && col0 >= 0 && (col0 & 7) == 0 && col0 + N <= ld) : col0 == 0; }
+static int resid_args(const mgk_resid_desc* d, ResidArgs& r) {
+    if (!d || !d->X || !d->W || !d->h || !d->part) return MG_E_ARG;
+    if (d->K < 64 || (d->K & 63) || d->N < 32 || (d->N & 31) || d->M < 1 || d->M > 256) return MG_E_SHAPE;
+    if (d->x_pk && !d->gain) return MG_E_ARG;
+    if (!kwin_ok(d->x_kts, d->x_k0, d->K) || !cwin_ok(d->x_ld, d->x_col0, d->N) || !cwin_ok(d->x2_ld, d->x2_col0, d->N)) return MG_E_SHAPE;
+    if (!rs_ok(d->rs_part, d->rs_nparts) || d->wide_tiles < 0 || d->wide_tiles > 8 || (!d->kpart != !d->ticket)) return MG_E_SHAPE;
+    r.X = (const uint16_t*)d->X; r.x_kts = d->x_kts; r.x_k0 = d->x_k0; r.W = (const uint16_t*)d->W; r.h = d->h; r.gain = d->gain; r.gscale = d->gscale;
+    r.x_pk = (uint16_t*)d->x_pk; r.x_ld = d->x_ld; r.x_col0 = d->x_col0; r.x2_pk = (uint16_t*)d->x2_pk; r.x2_ld = d->x2_ld; r.x2_col0 = d->x2_col0;
+    r.part = d->part; r.M = d->M; r.N = d->N; r.K = d->K; r.rs = RowScale{d->rs_part, d->rs_nparts, d->rs_inv_d, d->rs_eps};
+    r.alone = d->alone; r.wide_tiles = d->wide_tiles; r.kpart = d->kpart; r.ticket = d->ticket;
+    return MG_OK;
+}
+int mgk_gemm_resid_ex(void* stream, const mgk_resid_desc* d) {
     ResidArgs r{};
-    r.X = (const uint16_t*)X_pk; r.W = (const uint16_t*)W_pk; r.h = h; r.gain = gain; r.gscale = gscale; r.x_pk = (uint16_t*)x_pk;
-    r.part = part; r.M = M; r.N = N; r.K = K; r.rs = RowScale{rs_part, rs_nparts, rs_inv_d, rs_eps};
+    if (const int rc = resid_args(d, r)) return rc;
     gemm_rows_resid(r, (mgStream_t)stream);
     return MG_OK;
+}
+int mgk_gemm_pair_ex(void* stream, const mgk_resid_desc* d, const mgk_proj_desc* p, int epi) {
+    ResidArgs r{};
+    if (const int rc = resid_args(d, r)) return rc;
+    if (!p || !p->X || !p->W) return MG_E_ARG;
+    if (epi != EPI_HEADS && epi != EPI_PK_RELU && epi != EPI_F32_STORE) return MG_E_UNSUPPORTED;
+    if (r.kpart) return MG_E_ARG;                                        // (the pair launch has no K-slab form)
+    if (p->K < 64 || (p->K & 63) || p->N < 16 || (p->N & 15) || !kwin_ok(p->x_kts, p->x_k0, p->K) || !rs_ok(p->rs_part, p->rs_nparts)) return MG_E_SHAPE;
+    GemmArgs g{};
+    g.X = (const uint16_t*)p->X; g.x_kts = p->x_kts; g.x_k0 = p->x_k0; g.W = (const uint16_t*)p->W; g.M = r.M; g.N = p->N; g.K = p->K;
+    g.rs = RowScale{p->rs_part, p->rs_nparts, p->rs_inv_d, p->rs_eps}; g.both_halves = p->both_halves;
+    if (epi == EPI_HEADS) {
+        if (!p->q) return MG_E_ARG;
+        if (p->N & 63) return MG_E_SHAPE;
+        g.heads.ptr[0] = (uint16_t*)p->q; g.heads.fmt[0] = HF_STEP_Q; g.heads.inner = p->N; g.heads.H = p->N >> 6; g.heads.S_in = r.M;
+    } else if (epi == EPI_PK_RELU) {
+        if (!p->out_pk) return MG_E_ARG;
+        g.out_pk = (uint16_t*)p->out_pk;
+    } else {
+        if (!p->out_f32) return MG_E_ARG;
+        if (p->ldo < p->N || (p->ldo & 3)) return MG_E_SHAPE;
+        g.out_f32 = p->out_f32; g.ldo = p->ldo;
+    }
+    gemm_rows_pair(r, g, epi, (mgStream_t)stream);
+    return MG_OK;
+}
+
+int mgk_gemm_resid(void* stream, const void* X_pk, const void* W_pk, float* h, const float* gain, float gscale, void* x_pk,
+                   float* part, int M, int N, int K, const float* rs_part, int rs_nparts, float rs_inv_d, float rs_eps) {
+    return mgk_gemm_resid_mt(stream, X_pk, W_pk, h, gain, gscale, x_pk, part, M, N, K, rs_part, rs_nparts, rs_inv_d, rs_eps, 0, nullptr, nullptr);
 }
 
 int mgk_gemm_resid_mt(void* stream, const void* X_pk, const void* W_pk, float* h, const float* gain, float gscale, void* x_pk,
@@ -416,8 +506,12 @@ int mgk_gemm_pair(void* stream, const void* Wn_pk, const void* Wr_pk, const floa
     r.x2_pk = (uint16_t*)hb_out_pk; r.part = part; r.M = M; r.N = d; r.K = inner;
     GemmArgs g{};
     g.X = (const uint16_t*)xwin_pk; g.W = (const uint16_t*)W2_pk; g.M = M; g.N = N2; g.K = K2; g.out_pk = (uint16_t*)out2_pk;
-    if (!relu) return MG_E_UNSUPPORTED;      // the per-head form is covered through mg_generate
-    gemm_rows_pair(r, g, EPI_PK_RELU, st);
+    if (!relu) {                             // the per-head form: out2_pk = q [M][N2 / 64][64] bf16 (N2 = H * 64)
+        if (N2 & 63) return MG_E_SHAPE;
+        g.out_pk = nullptr;
+        g.heads.ptr[0] = (uint16_t*)out2_pk; g.heads.fmt[0] = HF_STEP_Q; g.heads.inner = N2; g.heads.H = N2 >> 6; g.heads.S_in = M;
+    }
+    gemm_rows_pair(r, g, relu ? EPI_PK_RELU : EPI_HEADS, st);
     return MG_OK;
 }
 

@@ -554,6 +554,7 @@ MG_DEV void shift_rows(GemmArgs& a, int rt) {
             else if (a.heads.fmt[ri] == HF_STEP_KV && !a.heads.row_map) a.heads.ptr[ri] += (size_t)rt * 32 * a.heads.H * (size_t)a.heads.S_cap * 64;
         }
         if (a.heads.row_map) a.heads.row_map += 32 * rt;
+        if (a.heads.pos_rows) a.heads.pos_rows += 32 * rt;      // (indexed by the call's row like row_map: without this a tile's rows took tile 0's positions)
     }
     if (a.rs.part) a.rs.part += (size_t)rt * 32 * a.rs.nparts;
     a.M -= 32 * rt;

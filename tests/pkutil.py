@@ -70,3 +70,21 @@ def untile_f32(t, N):
     """inverse of tile_f32 -> fp32 [rows stored][N] (padding rows included)."""
     Mp = t.size // N
     return np.ascontiguousarray(np.asarray(t, np.float32).reshape(Mp // 32, N // 4, 32, 4).transpose(0, 2, 1, 3)).reshape(Mp, N)
+
+
+def pack_tile_bits(bits2d):
+    """uint16 bit patterns [Rp][K] (Rp a multiple of 32) -> the packed tile format, flattened: inverse of unpack_tile_bits."""
+    Rp, K = bits2d.shape
+    t = np.asarray(bits2d, np.uint16).reshape(Rp // 32, 32, K // 16, 2, 8)
+    return np.ascontiguousarray(t.transpose(0, 2, 3, 1, 4)).reshape(-1)
+
+
+def window_bits(x, ld, col0, fill_bits, rows_pad=None):
+    """A packed buffer of `ld` columns whose columns [col0, col0 + x.shape[1]) hold bf16(x) in rows [0, x.shape[0]) and whose every other
+    element (other columns, padding rows) holds the bit pattern `fill_bits`: an activation WINDOW of a wider buffer (x_kts / x_k0 of the
+    decode-step kernels: k-tile window [col0 / 16, (col0 + K) / 16)) or the target of a column-window output (x2_ld / x2_col0)."""
+    R, K = x.shape
+    Rp = rows_pad if rows_pad is not None else (R + 31) // 32 * 32
+    b = np.full((Rp, ld), fill_bits, np.uint16)
+    b[:R, col0:col0 + K] = bf16_bits(x)
+    return pack_tile_bits(b)

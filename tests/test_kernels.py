@@ -192,9 +192,10 @@ def test_gemm_heads_step(be_name):
     x, w = rnd((rows, K), 12), rnd((3 * inner, K), 13, 0.2)
     ref = (pk.bf16_round(x) @ pk.bf16_round(w).T).reshape(rows, 3, H, 64)
     X, W = be.buf(pk.pack_tiles(x)), be.buf(pk.pack_tiles(w))
-    q = be.zeros((rows, H, 64), np.uint16)
-    kc = be.zeros((rows, H, T, 64), np.uint16)
-    vc = be.zeros((rows, H, T, 64), np.uint16)
+    sent = 0xBEEF                             # a bf16 bit pattern no projection leaves behind: what is not written keeps it
+    q = be.buf(np.full((rows, H, 64), sent, np.uint16))
+    kc = be.buf(np.full((rows, H, T, 64), sent, np.uint16))
+    vc = be.buf(np.full((rows, H, T, 64), sent, np.uint16))
     pos = 5
     rc = be.lib.mgk_gemm_heads(be.stream, 1, be.p(X), be.p(W), rows, 3 * inner, K, be.p(q), be.p(kc), be.p(vc),
                                HF_STEP_Q, HF_STEP_KV, HF_STEP_KV, H, rows, T, None, pos)
@@ -202,7 +203,8 @@ def test_gemm_heads_step(be_name):
     np.testing.assert_allclose(pk.bf16_to_f32(q.numpy()), ref[:, 0], rtol=1 / 128, atol=1e-3)
     np.testing.assert_allclose(pk.bf16_to_f32(kc.numpy())[:, :, pos], ref[:, 1], rtol=1 / 128, atol=1e-3)
     np.testing.assert_allclose(pk.bf16_to_f32(vc.numpy())[:, :, pos], ref[:, 2], rtol=1 / 128, atol=1e-3)
-    assert np.all(kc.numpy()[:, :, :pos] == 0) and np.all(kc.numpy()[:, :, pos + 1:] == 0)
+    for c in (kc.numpy(), vc.numpy()):
+        assert np.all(c[:, :, :pos] == sent) and np.all(c[:, :, pos + 1:] == sent)
 
 
 @pytest.mark.parametrize("be_name", BACKENDS)
