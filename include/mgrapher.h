@@ -141,6 +141,49 @@ int mg_generate_scored(mg_model* m, void* stream, void* ws, size_t ws_bytes, con
 
 /* Limits: B * num_beams <= 256 live sequences per call (MG_E_UNSUPPORTED beyond; split the batch), num_beams <= 8. */
 
+/* Sampled generation (stock generation/utils.py::_sample with do_sample = True): mg_generate's arguments without the beam ones, plus the
+ * options below.  Per live row and step, in stock's warper order: MinLength (EOS removed while the column written is below min_length),
+ * temperature (x / T, T > 0), top-k (every token >= the k-th largest value survives, ties included; 0 = off; k clamped to the vocabulary),
+ * top-p (a token of value v survives iff the probability mass of the surviving tokens with value <= v exceeds 1 - top_p - stock's rule with
+ * the tokens tied at the boundary kept; >= 1 = off; at least one token survives), then one draw from the survivors.
+ *   Randomness is counter-based, Philox4x32-10: key = seed, counter = (stream id lo, stream id hi, column written, 0); the two low output
+ * words form a 64-bit r and the token is the inverse CDF at r / 2^64 over the survivors in TOKEN-INDEX order.  All of it is integer
+ * arithmetic on fixed-point masses (csrc/k_sample.hip), so a call is reproducible run to run, and a row's draws depend on (seed, stream id,
+ * column, its own logits) only: with the cross-attention form pinned (mg_set_cross_absorb 0 or 1) a row's ids do not depend on the size of
+ * its call or on its place in it.
+ *   num_return    samples per image: R = B * num_return <= 256 decode rows, row b * num_return + j = sample j of image b (stock's order for
+ *                 num_return_sequences), each with its own self-attention cache; the encoder and the cross K/V (or the compacted encoder
+ *                 states) are computed once per image and read by its rows through a row -> image map.  The rows are greedy-form rows:
+ *                 the cross-attention form follows mg_set_cross_absorb by R, as for a greedy call of R rows.
+ *   stream_ids    [B * num_return] u64 device, nullable: the rows' stream ids (NULL: the row index)
+ *   token_scores  [B * num_return][max_length - 1] f32 device, nullable: the log-probability of each drawn token under the warped
+ *                 (filtered, renormalised) distribution - stock compute_transition_scores(sequences, scores, normalize_logits=True) on its
+ *                 processed scores; 0.0 after a row's EOS
+ * out_ids [B * num_return][max_length]; *out_cols_host as mg_generate; step_top2 [max_length][B * num_return][2] nullable (top-2 of the
+ * logits before temperature).
+ * WORKSPACE: size it with mg_sampled_workspace_bytes (below), NOT with mg_workspace_bytes.  For num_return = 1 the two agree.  For
+ * num_return > 1 they do not: mg_workspace_bytes(num_beams = num_return) sizes a beam-search call, whose cross-attention buffers follow
+ * mg_set_beam_cross_absorb, while a sampled call's rows are greedy rows and follow mg_set_cross_absorb by B * num_return; a workspace
+ * sized for the one may be too small for the other (MG_E_WORKSPACE).  mg_workspace_bytes keeps reporting exactly what beam search needs.
+ * Runs under the decode
+ * graph like the other batch forms (every option is part of the captured step's key); mg_debug_decode_capture's logits capture works, its
+ * forced ids do not (MG_E_UNSUPPORTED).  Vocabulary <= 36 864 (the selection keeps the row in registers).
+ * NOT built: the queue forms (mg_generate_stream*) and the OCR stage under sampling, one cross-attention pass shared by the samples of an
+ * image (the beam form's group = num_return), a Gumbel-max variant on the fused lm_head tail, beam-sample. */
+typedef struct mg_sample_opts {
+    float temperature;
+    int top_k;
+    float top_p;
+    uint64_t seed;
+    const uint64_t* stream_ids;
+    int num_return;
+    float* token_scores;
+} mg_sample_opts;
+int mg_sampled_workspace_bytes(const mg_model* m, int B, int L, int num_return, int max_length, int M_e1, size_t* out_bytes);
+int mg_generate_sampled(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
+                        const uint8_t* attention_mask, const float* pixel_values, const float* e1, int M_e1, int B, int L, int max_length,
+                        int min_length, int64_t* out_ids, int* out_cols_host, float* step_top2, const mg_sample_opts* opts);
+
 /* Continuous greedy decoding of N images - what the reference's evaluation loop does one image at a time with
  * model.generate(**encoding, num_beams=1, max_length=512) until EOS (/root/reference/markushgrapher/utils/ocsr/utils_evaluation.py:140,
  * 269-285), for a whole queue of images: `slots` decode rows work through the queue, a row that ends (EOS / max_length) frees its
@@ -386,6 +429,17 @@ size_t mgk_embed_meta_bytes(int B, int S_cap);
 int mgk_greedy_select(void* stream, const float* logits, int rows, int V, int ldl, int eos, int pad, int min_len,
                       int64_t* next_ids, int64_t* out_ids, int max_len, int pos, int* unfinished, int* n_unfinished,
                       float* top2);
+
+/* Sampled selection of one decode step (csrc/k_sample.hip), the kernel mg_generate_sampled launches: for every row with unfinished != 0
+ * MinLength (EOS removed while pos < min_len), temperature, top-k (0 = off), top-p (>= 1 = off) and one Philox4x32-10 draw at counter
+ * (stream id, pos); finished rows emit pad.  logits [rows][ldl] fp32, ldl a multiple of 4 >= V, V <= 36 864 (MG_E_UNSUPPORTED beyond);
+ * stream_ids [rows] u64 device, nullable (the row index); token_scores [rows][ts_ld] nullable, column pos - 1 written. */
+int mgk_sample_select(void* stream, const float* logits, int rows, int V, int ldl, int eos, int pad, int min_len, float temperature,
+                      int top_k, float top_p, uint64_t seed, const uint64_t* stream_ids, int64_t* next_ids, int64_t* out_ids, int max_len,
+                      int pos, int* unfinished, int* n_unfinished, float* token_scores, int ts_ld);
+/* The generator itself, on the host: out_host[4] = Philox4x32-10 with key = seed and counter = (stream_id lo, stream_id hi, pos, 0).
+ * The draw uses r = out[1] << 32 | out[0]. */
+int mgk_philox(uint64_t seed, uint64_t stream_id, uint32_t pos, uint32_t* out_host);
 
 /* ---- kernels of the OCSR vision branch "e1" (csrc/k_swin.hip; test entries, not on the product path) ---- */
 /* (Shifted-)window attention of one Swin block, head dim 32.  qkv_pk packed bf16 [B*R*R padded to 32][3C] = [q | k | v] in the natural token

@@ -307,6 +307,30 @@ int mgk_greedy_select_scored(void* stream, const float* logits, int rows, int V,
     return MG_OK;
 }
 
+// sample_select at operator level (k_sample.hip): one launch over `rows` rows at column `pos`; token_scores [rows][ts_ld] nullable
+int mgk_sample_select(void* stream, const float* logits, int rows, int V, int ldl, int eos, int pad, int min_len, float temperature,
+                      int top_k, float top_p, uint64_t seed, const uint64_t* stream_ids, int64_t* next_ids, int64_t* out_ids, int max_len,
+                      int pos, int* unfinished, int* n_unfinished, float* token_scores, int ts_ld) {
+    if (!logits || !next_ids || !out_ids || !unfinished || !n_unfinished || rows < 1 || ldl < V || (ldl & 3)) return MG_E_ARG;
+    if (!(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f)) return MG_E_ARG;
+    if (!sample_select_supported(V)) return MG_E_UNSUPPORTED;
+    SampleArgs a{};
+    a.logits = logits; a.rows = rows; a.V = V; a.ldl = ldl; a.eos = eos; a.pad = pad; a.min_len = min_len;
+    a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.seed = seed; a.stream_ids = stream_ids;
+    a.next_ids = next_ids; a.out_ids = out_ids; a.max_len = max_len; a.pos = pos; a.unfinished = unfinished;
+    a.n_unfinished = n_unfinished; a.token_scores = token_scores; a.ts_ld = ts_ld;
+    mg_memset_async(n_unfinished, 0, sizeof(int), (mgStream_t)stream);   // the kernel accumulates
+    sample_select(a, (mgStream_t)stream);
+    return MG_OK;
+}
+
+// the generator of sample_select on the host: out_host[4] = Philox4x32-10(key = seed, counter = (stream_id lo, stream_id hi, pos, 0))
+int mgk_philox(uint64_t seed, uint64_t stream_id, uint32_t pos, uint32_t* out_host) {
+    if (!out_host) return MG_E_ARG;
+    philox4x32_10(seed, stream_id, pos, out_host);
+    return MG_OK;
+}
+
 // The lm_head form of the fused greedy tail (gemm_rows_splitk with TopOut, KS = 1): P [M][ldp] logits (nullable: not written),
 // ptop [M][ceil(N/32)] float4 partials, stopv [M][4]; stop token `eos` kept apart; lse = TopOut::lse
 int mgk_lm_head_top(void* stream, const void* X_pk, const void* W_pk, float* P, int M, int N, int K, int ldp, void* ptop, float* stopv,

@@ -60,11 +60,17 @@ struct StepGraph {
         // scored calls (mg_gen_opts): the selection / slot-end launches hold the token-score and beam-index pointers and the n-best count
         const void *token_scores, *beam_indices;
         int num_return;
+        // sampled calls (mg_sample_opts): the selection launch holds every one of these by value (temperature 0 = not a sampled call)
+        float temperature, top_p;
+        int top_k;
+        uint64_t seed;
+        const void* stream_ids;
         bool operator==(const Key& o) const {
             return ws == o.ws && out_ids == o.out_ids && top2 == o.top2 && stream == o.stream && B == o.B && L == o.L && K == o.K && M_e1 == o.M_e1 &&
                    max_length == o.max_length && min_length == o.min_length && early_stopping == o.early_stopping &&
                    length_penalty == o.length_penalty && scores == o.scores && token_scores == o.token_scores &&
-                   beam_indices == o.beam_indices && num_return == o.num_return;
+                   beam_indices == o.beam_indices && num_return == o.num_return && temperature == o.temperature && top_p == o.top_p &&
+                   top_k == o.top_k && seed == o.seed && stream_ids == o.stream_ids;
         }
     };
     Key key{};
@@ -323,7 +329,9 @@ struct Carver {
     }
 };
 
-void carve(const mg_model* m, char* base, int B, int L, int K, int max_len, int T, int Me1, Ws* w) {
+// form_K > 0: the cross-attention form (absorbed or K / V) is chosen as for form_K rows per image instead of K (sampled calls: K = samples
+// per image for the row counts, form_K = 1 - their rows are greedy rows)
+void carve(const mg_model* m, char* base, int B, int L, int K, int max_len, int T, int Me1, Ws* w, int form_K = 0) {
     Carver c{base};
     const int d = m->d, inner = m->inner, H = m->H;
     const int S_cap = round_up(L + m->P, 64);
@@ -371,11 +379,12 @@ void carve(const mg_model* m, char* base, int B, int L, int K, int max_len, int 
         const int R = B * K, Rp = round_up(R, 32);
         const size_t nl = m->dec.size();
         w->xk = w->xv = w->encx = w->qx = w->xpart = nullptr; w->xml = nullptr;
-        if (use_absorb(m, K, R)) {
+        const int fK = form_K > 0 ? form_K : K;
+        if (use_absorb(m, fK, R)) {
             w->encx = c.take<uint16_t>((size_t)B * Sx_cap * d);
             w->qx = c.take<uint16_t>((size_t)Rp * H * d);
-            w->xpart = c.take<uint16_t>((size_t)Rp * xa_nsplit(m, K) * H * d);
-            w->xml = c.take<float>((size_t)Rp * xa_nsplit(m, K) * H * 2);
+            w->xpart = c.take<uint16_t>((size_t)Rp * xa_nsplit(m, fK) * H * d);
+            w->xml = c.take<float>((size_t)Rp * xa_nsplit(m, fK) * H * 2);
         } else {
             w->xk = c.take<uint16_t>(nl * B * H * Sx_cap * 64);
             w->xv = c.take<uint16_t>(nl * B * H * Sx_cap * 64);
@@ -637,6 +646,7 @@ struct DecodeCtx {
     // scored calls: greedy token log-probabilities [rows or images][max_length - 1] (nullable); beam queue: the n-best output
     float* token_scores;
     BeamOut nbest;
+    const mg_sample_opts* samp;   // sampled call (mg_generate_sampled): the selection is sample_select; rows of an image read its K/V through slots.pool
 };
 
 // Decode step, 6 launches per layer: QKV -> self-attention -> [O residual | cross-Q] -> cross-attention ->
@@ -773,7 +783,15 @@ static void decode_step(mg_model* m, const DecodeCtx& c, int t, const int* tdev,
         g.step_ctr = stream ? nullptr : counters;      // the last workgroup to finish does the step bookkeeping (no step_end launch)
         g.slots = c.slots;
         g.token_scores = c.token_scores; g.ts_ld = max_length - 1;
-        if (fused_tail) {
+        if (c.samp) {
+            SampleArgs sa{};
+            sa.logits = c.logits; sa.rows = R; sa.V = m->V; sa.ldl = ldl; sa.eos = g.eos; sa.pad = g.pad; sa.min_len = min_length;
+            sa.temperature = c.samp->temperature; sa.top_k = c.samp->top_k; sa.top_p = c.samp->top_p; sa.seed = c.samp->seed;
+            sa.stream_ids = c.samp->stream_ids; sa.next_ids = c.next_ids; sa.out_ids = out_ids; sa.max_len = max_length;
+            sa.pos = g.pos; sa.pos_dev = tdev; sa.unfinished = c.unfinished; sa.n_unfinished = g.n_unfinished; sa.top2 = g.top2;
+            sa.step_ctr = counters; sa.token_scores = c.token_scores; sa.ts_ld = max_length - 1;
+            sample_select(sa, st);
+        } else if (fused_tail) {
             g.ptop = c.ptop; g.stopv = c.stopv; g.ntiles = ldl / 32;
             g.tok_emb = m->at<uint16_t>(m->tok_emb); g.h = c.dh; g.gain = m->at<float>(m->dec[0].ln0); g.x_pk = c.dx_pk;
             g.x2_pk = c.xa; g.x2_ld = K2; g.x2_col0 = 0; g.d = d; g.eps = eps;
@@ -1142,6 +1160,15 @@ int mg_workspace_bytes(const mg_model* m, int B, int L, int num_beams, int max_l
     return MG_OK;
 }
 
+int mg_sampled_workspace_bytes(const mg_model* m, int B, int L, int num_return, int max_length, int M_e1, size_t* out_bytes) {
+    if (!m || !out_bytes || B < 1 || L < 1 || num_return < 1 || max_length < 0 || M_e1 < 0) return fail(MG_E_ARG, "mg_sampled_workspace_bytes: bad argument");
+    Ws w;
+    if (M_e1 == 0) M_e1 = m->e1_M;
+    carve(m, nullptr, B, L, num_return, max_length, 0, M_e1, &w, 1);      // rows of num_return per image, cross-attention form of greedy rows
+    *out_bytes = w.total;
+    return MG_OK;
+}
+
 int mg_encode(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
               const uint8_t* attention_mask, const float* pixel_values, const float* e1, int M_e1, int B, int L, float* enc_out,
               uint8_t* enc_mask) {
@@ -1333,20 +1360,46 @@ int mg_generate(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int6
                               min_length, length_penalty, early_stopping, out_ids, out_cols_host, out_scores, step_top2, nullptr);
 }
 
-int mg_generate_scored(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
-                       const uint8_t* attention_mask, const float* pixel_values, const float* e1, int M_e1, int B, int L, int num_beams,
-                       int max_length, int min_length, float length_penalty, int early_stopping, int64_t* out_ids, int* out_cols_host,
-                       float* out_scores, float* step_top2, const mg_gen_opts* opts) {
+}  // extern "C"
+
+// owner[r] = r / group: the image whose encoder states row r of a sampled call reads
+__global__ void row_owner_kernel(int* owner, int rows, int group) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < rows) owner[r] = r / group;
+}
+
+// mg_generate_scored (samp == nullptr) and mg_generate_sampled (samp given, num_beams = 1, opts = nullptr).  A sampled call decodes
+// R = B * samp->num_return greedy-form rows (K = 1: no ancestor table, no beam state), the rows of an image reading its cross K/V (or
+// its encoder states) through the row -> owner map; its selection is sample_select on the unfused tail.
+static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
+                         const uint8_t* attention_mask, const float* pixel_values, const float* e1, int M_e1, int B, int L, int num_beams,
+                         int max_length, int min_length, float length_penalty, int early_stopping, int64_t* out_ids, int* out_cols_host,
+                         float* out_scores, float* step_top2, const mg_gen_opts* opts, const mg_sample_opts* samp, const char* who) {
     entry_drain();
-    if (!m || !out_ids || !out_cols_host) return fail(MG_E_ARG, "mg_generate: null argument");
-    MG_ONE_CALL(m, "mg_generate");
+    if (!m || !out_ids || !out_cols_host) return fail(MG_E_ARG, "%s: null argument", who);
+    std::unique_lock<std::recursive_mutex> call_lock(m->call_mu, std::try_to_lock);      // MG_ONE_CALL under the entry's own name
+    if (!call_lock.owns_lock())
+        return fail(MG_E_STATE, "%s: this execution context is inside another call (one call at a time per context; mg_clone gives further contexts)", who);
     const int num_return = opts ? opts->num_return : 1;
     if (num_return < 1 || num_return > num_beams)
-        return fail(MG_E_ARG, "mg_generate: num_return (%d) must be in [1, num_beams = %d]", num_return, num_beams);
+        return fail(MG_E_ARG, "%s: num_return (%d) must be in [1, num_beams = %d]", who, num_return, num_beams);
     float* token_scores = opts ? opts->token_scores : nullptr;
+    const int NS = samp ? samp->num_return : 1;      // samples per image
+    if (samp) {
+        if (!(samp->temperature > 0.f)) return fail(MG_E_ARG, "mg_generate_sampled: temperature must be > 0");
+        if (samp->top_k < 0) return fail(MG_E_ARG, "mg_generate_sampled: top_k must be >= 0 (0 = off)");
+        if (!(samp->top_p > 0.f)) return fail(MG_E_ARG, "mg_generate_sampled: top_p must be > 0 (>= 1 = off)");
+        if (NS < 1) return fail(MG_E_ARG, "mg_generate_sampled: num_return must be >= 1");
+        if ((long)B * NS > 256)
+            return fail(MG_E_UNSUPPORTED, "mg_generate_sampled: B * num_return = %ld live sequences exceeds the supported 256; split the batch",
+                        (long)B * NS);
+        if (!sample_select_supported(m->V)) return fail(MG_E_UNSUPPORTED, "mg_generate_sampled: vocabulary of %d exceeds the selection kernel's 36864", m->V);
+        if (m->dbg_forced) return fail(MG_E_UNSUPPORTED, "mg_generate_sampled: forced ids (mg_debug_decode_capture) are not supported under sampling");
+        token_scores = samp->token_scores;
+    }
     int32_t* beam_indices = opts ? opts->beam_indices : nullptr;
-    if (max_length < 2 || max_length > m->T_cap) return fail(MG_E_SHAPE, "mg_generate: max_length must be in [2, %d]", m->T_cap);
-    if (num_beams < 1 || num_beams > 8) return fail(MG_E_UNSUPPORTED, "mg_generate: num_beams must be in [1, 8]");
+    if (max_length < 2 || max_length > m->T_cap) return fail(MG_E_SHAPE, "%s: max_length must be in [2, %d]", who, m->T_cap);
+    if (num_beams < 1 || num_beams > 8) return fail(MG_E_UNSUPPORTED, "%s: num_beams must be in [1, 8]", who);
     // the decode-step projections keep all live rows of a workgroup's feature slice in registers: at most 8 row tiles
     if ((long)B * num_beams > 256)
         return fail(MG_E_UNSUPPORTED, "mg_generate: B * num_beams = %ld live sequences exceeds the supported 256; split the batch",
@@ -1354,16 +1407,17 @@ int mg_generate_scored(mg_model* m, void* stream, void* ws, size_t ws_bytes, con
     mgStream_t st = (mgStream_t)stream;
     const int K = num_beams;
     Ws w;
-    if ((e1 == nullptr) != (M_e1 == 0) || M_e1 < 0) return fail(MG_E_ARG, "mg_generate: e1 and M_e1 must be given together");
+    if ((e1 == nullptr) != (M_e1 == 0) || M_e1 < 0) return fail(MG_E_ARG, "%s: e1 and M_e1 must be given together", who);
     const int M_in = M_e1;
     if (!e1 && m->e1m) M_e1 = m->e1_M;            // attached OCSR branch: mg_encode evaluates it (same workspace layout as with precomputed tokens)
-    carve(m, (char*)ws, B, L, K, max_length, 0, M_e1, &w);
-    if (w.total > ws_bytes) return fail(MG_E_WORKSPACE, "mg_generate: workspace too small (%zu < %zu)", ws_bytes, w.total);
+    if (samp) carve(m, (char*)ws, B, L, NS, max_length, 0, M_e1, &w, 1);
+    else carve(m, (char*)ws, B, L, K, max_length, 0, M_e1, &w);
+    if (w.total > ws_bytes) return fail(MG_E_WORKSPACE, "%s: workspace too small (%zu < %zu)", who, ws_bytes, w.total);
     if (m->phase_on) mg_event_record(m->phase_ev[0], st);
     int rc = mg_encode(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, e1, M_in, B, L, nullptr, nullptr);
     if (rc != MG_OK) return rc;
     const int d = m->d, H = m->H, inner = m->inner, S_cap = m->st_Scap, M = B * S_cap;
-    const int R = B * K, T_cap = m->T_cap;
+    const int R = B * K * NS, T_cap = m->T_cap;
     const size_t nl = m->dec.size();
     const int M64 = M_e1 > 0 ? round_up(M_e1, 64) : 0, Sx_cap = S_cap + M64;
     const size_t xkv_stride = (size_t)B * H * Sx_cap * 64, skv_stride = (size_t)R * H * T_cap * 64;
@@ -1433,11 +1487,17 @@ int mg_generate_scored(mg_model* m, void* stream, void* ws, size_t ws_bytes, con
     dc.length_penalty = length_penalty; dc.out_ids = out_ids; dc.step_top2 = step_top2; dc.live = live;
     if (K == 1 && token_scores) {      // columns a row does not reach (after its EOS, after the last step) hold 0
         dc.token_scores = token_scores;
-        mg_memset_async(token_scores, 0, (size_t)B * (max_length - 1) * sizeof(float), st);
+        mg_memset_async(token_scores, 0, (size_t)R * (max_length - 1) * sizeof(float), st);
+    }
+    dc.samp = samp;
+    if (samp && NS > 1) {              // (the ancestor table's buffer is free: a sampled call has no beams.  The live-row skip of the attention
+                                       // launches is per ROW in both cross-attention forms, so the samples of an image finish independently)
+        MG_LAUNCH(row_owner_kernel, dim3((R + 255) / 256), dim3(256), 0, st, w.anc, R, NS);
+        dc.slots.pool = w.anc;
     }
     // greedy batch calls run the fused tail (lm_head top-2 partials -> selection + next embedding in one launch); the parity
     // instrumentation needs the full logits / overrides the fed token, and d_model > 2048 would change the norm's summation order
-    const bool fused_tail = K == 1 && m->fused_tail && !m->dbg_logits && !m->dbg_forced && d <= 2048;
+    const bool fused_tail = K == 1 && !samp && m->fused_tail && !m->dbg_logits && !m->dbg_forced && d <= 2048;
     if (fused_tail) {
         dc.ptop = w.ptop; dc.stopv = w.stopv;
         embed_norm_rows(w.next_ids, m->at<uint16_t>(m->tok_emb), w.dh, m->at<float>(m->dec[0].ln0), w.dx_pk, w.xa, d + inner, 0, R, d, m->V,
@@ -1449,7 +1509,8 @@ int mg_generate_scored(mg_model* m, void* stream, void* ws, size_t ws_bytes, con
 #ifndef MG_EMU
     if (m->use_graph == 1 && !instrumented) {
         const StepGraph::Key key{ws, out_ids, step_top2, (const void*)st, B, L, K, max_length, min_length, early_stopping, M_e1, length_penalty, nullptr,
-                                 dc.token_scores, nullptr, 1};
+                                 dc.token_scores, nullptr, samp ? NS : 1, samp ? samp->temperature : 0.f, samp ? samp->top_p : 0.f,
+                                 samp ? samp->top_k : 0, samp ? samp->seed : 0, samp ? (const void*)samp->stream_ids : nullptr};
         StepGraph& sg = m->step_graph;
         if (!(sg.valid && sg.key == key)) {
             std::lock_guard<std::mutex> capture_lock(mg_capture_mutex());
@@ -1466,7 +1527,7 @@ int mg_generate_scored(mg_model* m, void* stream, void* ws, size_t ws_bytes, con
                 if (graph) (void)hipGraphDestroy(graph);
             }
             if (!sg.valid && getenv("MG_DEBUG"))
-                fprintf(stderr, "mg_generate: decode-step capture failed (begin %s, end %s, instantiate %s); launching eagerly\n",
+                fprintf(stderr, "%s: decode-step capture failed (begin %s, end %s, instantiate %s); launching eagerly\n", who,
                         hipGetErrorName(e1), hipGetErrorName(e2), hipGetErrorName(e3));
             (void)hipGetLastError();
         }
@@ -1489,7 +1550,7 @@ int mg_generate_scored(mg_model* m, void* stream, void* ws, size_t ws_bytes, con
         const bool timed_step = m->prof_every > 0 && (t % m->prof_every) == 0;
 #ifndef MG_EMU
         if (graphed && !timed_step) {
-            if (hipGraphLaunch(m->step_graph.exec, st) != hipSuccess) return fail(MG_E_HIP, "mg_generate: hipGraphLaunch failed");
+            if (hipGraphLaunch(m->step_graph.exec, st) != hipSuccess) return fail(MG_E_HIP, "%s: hipGraphLaunch failed", who);
         } else
 #endif
         {
@@ -1520,7 +1581,7 @@ int mg_generate_scored(mg_model* m, void* stream, void* ws, size_t ws_bytes, con
     int beam_cols = 0;
     if (K > 1) mg_memcpy_async(&beam_cols, counters + 4, sizeof(int), st);
     mg_stream_sync(st);
-    rc = check_launch("mg_generate");
+    rc = check_launch(who);
     if (rc != MG_OK) return rc;
     if (m->prof_used) {
         double keys = 0.0;
@@ -1538,10 +1599,28 @@ int mg_generate_scored(mg_model* m, void* stream, void* ws, size_t ws_bytes, con
         m->phase_dec_ms += mg_event_elapsed_ms(m->phase_ev[1], m->phase_ev[2]);
         m->phase_n += 1;
     }
-    if (host_flag[3] != 0) return fail(MG_E_INPUT, "mg_generate: %d token ids outside [0, vocab)", host_flag[3]);
+    if (host_flag[3] != 0) return fail(MG_E_INPUT, "%s: %d token ids outside [0, vocab)", who, host_flag[3]);
     if (K == 1) *out_cols_host = 1 + (host_flag[1] >= 0 ? host_flag[1] + 1 : steps_done);
     else *out_cols_host = beam_cols;
     return MG_OK;
+}
+
+extern "C" {
+
+int mg_generate_scored(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
+                       const uint8_t* attention_mask, const float* pixel_values, const float* e1, int M_e1, int B, int L, int num_beams,
+                       int max_length, int min_length, float length_penalty, int early_stopping, int64_t* out_ids, int* out_cols_host,
+                       float* out_scores, float* step_top2, const mg_gen_opts* opts) {
+    return generate_impl(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, e1, M_e1, B, L, num_beams, max_length, min_length,
+                         length_penalty, early_stopping, out_ids, out_cols_host, out_scores, step_top2, opts, nullptr, "mg_generate");
+}
+
+int mg_generate_sampled(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
+                        const uint8_t* attention_mask, const float* pixel_values, const float* e1, int M_e1, int B, int L, int max_length,
+                        int min_length, int64_t* out_ids, int* out_cols_host, float* step_top2, const mg_sample_opts* opts) {
+    if (!opts) return fail(MG_E_ARG, "mg_generate_sampled: null options");
+    return generate_impl(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, e1, M_e1, B, L, 1, max_length, min_length, 1.0f,
+                         0, out_ids, out_cols_host, nullptr, step_top2, nullptr, opts, "mg_generate_sampled");
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -424,6 +424,42 @@ struct ArgmaxArgs {
 };
 void greedy_select(const ArgmaxArgs& a, mgStream_t stream);
 void greedy_select_fused(const ArgmaxArgs& a, mgStream_t stream);
+// Sampled selection (k_sample.hip; stock generation/utils.py::_sample with do_sample = True): MinLength, temperature, top-k, top-p in
+// stock's order, then one draw per live row.  Batch form only; bookkeeping (unfinished, n_unfinished, step_ctr, pos_dev, top2) as ArgmaxArgs.
+struct SampleArgs {
+    const float* logits;     // [rows][ldl]
+    int rows, V, ldl;
+    int eos, pad, min_len;
+    float temperature;       // > 0
+    int top_k;               // 0 = off; ties at the k-th largest value are all kept
+    float top_p;             // >= 1 = off; ties at the boundary value are all kept
+    uint64_t seed;           // Philox4x32-10 key
+    const uint64_t* stream_ids;   // [rows] counter words 0 / 1 of a row's stream (null: the row index); word 2 = the column written
+    int64_t* next_ids;
+    int64_t* out_ids;        // [rows][max_len]
+    int max_len, pos;
+    const int* pos_dev;
+    int* unfinished;
+    int* n_unfinished;
+    float* top2;             // nullable: top-1 / top-2 of the row's logits before temperature (MinLength applied); 0 for finished rows
+    int* step_ctr;
+    float* token_scores;     // nullable, [rows][ts_ld]: log-probability of the drawn token under the warped distribution, column pos - 1
+    int ts_ld;
+};
+bool sample_select_supported(int V);     // the row is held in registers: V <= 36 864
+void sample_select(const SampleArgs& a, mgStream_t stream);
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): key = seed, counter = (stream lo, stream hi, pos, 0)
+MG_HD void philox4x32_10(uint64_t seed, uint64_t stream_id, uint32_t pos, uint32_t out[4]) {
+    uint32_t c0 = (uint32_t)stream_id, c1 = (uint32_t)(stream_id >> 32), c2 = pos, c3 = 0;
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    for (int round = 0; round < 10; ++round) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
 // continuous decoding, after the selection of a step: idle slots take the next ready images of the queue (in slot order:
 // deterministic), live count / oldest live image / step counter are published for the host
 void slot_refill(const SlotTable& s, int64_t* next_ids, int* unfinished, int rows, mgStream_t stream);

@@ -33,6 +33,12 @@ class MgGenOpts(C.Structure):
     _fields_ = [("num_return", C.c_int), ("token_scores", C.c_void_p), ("seq_scores", C.c_void_p), ("beam_indices", C.c_void_p)]
 
 
+class MgSampleOpts(C.Structure):
+    """include/mgrapher.h mg_sample_opts: the options of mg_generate_sampled."""
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float), ("seed", C.c_uint64), ("stream_ids", C.c_void_p),
+                ("num_return", C.c_int), ("token_scores", C.c_void_p)]
+
+
 class TorchMem:
     """Device memory carried by torch tensors on one GPU."""
 
@@ -112,6 +118,7 @@ class Engine:
         self._ws = None
         self._ws_bytes = 0
         self._gen_out = {}
+        self._samp_out = {}
         self.ignored_keys = []
         self._e1_engine = None
 
@@ -140,6 +147,10 @@ class Engine:
                                   C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
                                   C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]
         L.mg_generate_scored.argtypes = L.mg_generate.argtypes + [C.POINTER(MgGenOpts)]
+        L.mg_sampled_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+        L.mg_generate_sampled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p,
+                                          C.POINTER(MgSampleOpts)]
         L.mg_stream_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         L.mg_generate_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + \
                                         [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.POINTER(C.c_long)]
@@ -214,6 +225,7 @@ class Engine:
         other.model = C.c_void_p()
         self._chk(self.lib.mg_clone(self.model, C.byref(other.model)))
         other._ws, other._ws_bytes, other._gen_out, other.ignored_keys = None, 0, {}, list(self.ignored_keys)
+        other._samp_out = {}
         other._e1_engine = self._e1_engine      # mg_clone carries the attachment; the branch's weights are shared and kept alive
         return other
 
@@ -224,7 +236,7 @@ class Engine:
         self.mem.sync()
         self._chk(self.lib.mg_attach_e1(self.model, e1_engine.model if e1_engine is not None else None))
         self._e1_engine = e1_engine
-        self._ws, self._ws_bytes, self._gen_out = None, 0, {}
+        self._ws, self._ws_bytes, self._gen_out, self._samp_out = None, 0, {}, {}
         self._sws, self._sws_bytes = None, 0
         return self
 
@@ -234,7 +246,7 @@ class Engine:
         that moves on to another stage with its own contexts gives the memory back first.  The captured decode graph replays on the
         workspace it was captured on, so the library forgets it as well (mg_set_decode_graph re-arms the capture)."""
         self.mem.sync()
-        self._ws, self._ws_bytes, self._gen_out = None, 0, {}
+        self._ws, self._ws_bytes, self._gen_out, self._samp_out = None, 0, {}, {}
         self._sws, self._sws_bytes = None, 0
         if self.model:
             prev = self.lib.mg_set_decode_graph(self.model, 0)
@@ -276,9 +288,14 @@ class Engine:
         k = self.lib.mg_debug_bucket_table(self.model, which, out, n)
         return np.array(out[:k], dtype=np.int32)
 
-    def workspace(self, B, L, num_beams, max_length, T, M_e1=0):
+    def workspace(self, B, L, num_beams, max_length, T, M_e1=0, sampled=False):
+        """The context's workspace, grown to what the call needs.  sampled: num_beams is the samples per image of a generate_sampled call
+        (mg_sampled_workspace_bytes: its rows choose the cross-attention form as greedy rows)."""
         need = C.c_size_t()
-        self._chk(self.lib.mg_workspace_bytes(self.model, B, L, num_beams, max_length, T, M_e1, C.byref(need)))
+        if sampled:
+            self._chk(self.lib.mg_sampled_workspace_bytes(self.model, B, L, num_beams, max_length, M_e1, C.byref(need)))
+        else:
+            self._chk(self.lib.mg_workspace_bytes(self.model, B, L, num_beams, max_length, T, M_e1, C.byref(need)))
         if need.value > self._ws_bytes:
             self._ws = None
             self._ws = self.mem.empty((need.value,), np.uint8)
@@ -399,6 +416,57 @@ class Engine:
         opts = MgGenOpts(1, self.mem.ptr(ts).value, self.mem.ptr(ss).value if ss is not None else None,
                          self.mem.ptr(bi).value if bi is not None else None)
         return opts, ts, ss, bi
+
+    def generate_sampled(self, input_ids, bbox, attention_mask, pixel_values, max_length=512, min_length=0, temperature=1.0, top_k=0,
+                         top_p=1.0, seed=0, num_return=1, stream_ids=None, return_scores=False, return_top2=False, e1=None):
+        """Sampled decoding (include/mgrapher.h mg_generate_sampled): temperature, top-k (0 = off), top-p (1 = off) in stock's order, one
+        Philox4x32-10 draw per live row and step at counter (stream id, column) under the key `seed`.  -> (ids [B * num_return, cols],
+        cols, token_scores [B * num_return, cols - 1] or None[, top2]): row b * num_return + j is sample j of image b.  stream_ids
+        [B * num_return] (default: the row index) name the rows' random streams: a row's draws depend on (seed, stream id, column) and its own
+        logits only."""
+        ids, bb, am, pv, B, L = self._inputs(input_ids, bbox, attention_mask, pixel_values)
+        nr = int(num_return)
+        if nr < 1:
+            raise ValueError(f"num_return must be >= 1, got {nr}")
+        if not float(temperature) > 0.0:
+            raise ValueError(f"temperature must be > 0, got {temperature}")
+        if int(top_k) < 0:
+            raise ValueError(f"top_k must be >= 0 (0 = off), got {top_k}")
+        if not 0.0 < float(top_p) <= 1.0:
+            raise ValueError(f"top_p must be in (0, 1], got {top_p}")
+        R = B * nr
+        if R > self.MAX_LIVE_ROWS:
+            raise MgError(f"generate_sampled: B * num_return = {R} live sequences exceeds the supported {self.MAX_LIVE_ROWS}; split the batch")
+        e1t, M = self._e1(e1, B)
+        ws, nb = self.workspace(B, L, nr, max_length, 0, M, sampled=True)
+        # persistent output / stream-id buffers: the captured decode step holds their addresses (see generate)
+        cache = self._samp_out
+        okey = (R, max_length)
+        if okey not in cache:
+            cache.clear()
+            cache[okey] = {"ids": self.mem.empty((R, max_length), np.int64), "ts": self.mem.zeros((R, max_length - 1), np.float32),
+                           "sid": None, "sid_host": None}
+        c = cache[okey]
+        sid = None
+        if stream_ids is not None:
+            host = np.ascontiguousarray(np.asarray(stream_ids).astype(np.uint64).reshape(-1))
+            if host.shape[0] != R:
+                raise ValueError(f"stream_ids must hold B * num_return = {R} ids, got {host.shape[0]}")
+            if c["sid_host"] is None or not np.array_equal(c["sid_host"], host):
+                c["sid"], c["sid_host"] = self.mem.asarray(host.view(np.int64), np.int64), host
+            sid = c["sid"]
+        top2 = self.mem.zeros((max_length, R, 2), np.float32) if return_top2 else None
+        opts = MgSampleOpts(float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                            self.mem.ptr(sid).value if sid is not None else None, nr,
+                            self.mem.ptr(c["ts"]).value if return_scores else None)
+        cols = C.c_int(0)
+        self._chk(self.lib.mg_generate_sampled(
+            self.model, self.mem.stream(), self.mem.ptr(ws), nb, self.mem.ptr(ids), self.mem.ptr(bb),
+            self.mem.ptr(am) if am is not None else None, self.mem.ptr(pv), self.mem.ptr(e1t) if e1t is not None else None, M, B, L,
+            max_length, min_length, self.mem.ptr(c["ids"]), C.byref(cols), self.mem.ptr(top2) if top2 is not None else None, C.byref(opts)))
+        n = cols.value
+        res = (self.mem.copy(c["ids"][:, :n]), n, self.mem.copy(c["ts"][:, :n - 1]) if return_scores else None)
+        return res + (top2,) if return_top2 else res
 
     def generate_stream(self, input_ids, bbox, attention_mask, pixel_values, max_length=512, min_length=0, chunk=32, slots=32,
                         pool_chunks=3, return_scores=False):

@@ -408,18 +408,88 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
                                                ignore_index=-100)
         return Seq2SeqLMOutput(loss=loss, logits=logits, encoder_last_hidden_state=enc, encoder_attention_mask=mask)
 
+    def _default_mask(self, input_ids, attention_mask):
+        if attention_mask is not None:
+            return attention_mask
+        pad, eos = self.config.pad_token_id, self.config.eos_token_id
+        if pad is not None and pad != eos and bool((input_ids == pad).any()):
+            return (input_ids != pad).long()
+        return torch.ones_like(input_ids)
+
+    def _generate_sampled(self, input_ids, bbox, pixel_values, attention_mask, num_beams, max_length, min_length, e1, num_return, as_dict,
+                          want_scores, want_logits, kw):
+        """generate(do_sample=True): stock `_sample` with the temperature / top-k / top-p warpers, drawn on the device
+        (include/mgrapher.h mg_generate_sampled).  temperature=1.0, top_k=None (generation_config.top_k if the model has one, else stock's
+        default 50; 0 = off), top_p=1.0, num_return_sequences=1, seed=None, stream_ids=None.
+        Reproducibility: seed=None draws the call's seed from torch's default CPU generator, so torch.manual_seed(s) makes a sequence of
+        calls reproducible and consecutive calls differ; an explicit seed is used as given.  A row's draws depend on (seed, its stream
+        id - by default its row index b * num_return_sequences + j - the column) and its own logits only.
+        -> [B * num_return_sequences, T], the samples of an image consecutive; return_dict_in_generate: GenerateOutput with token_scores
+        (the log-probability of every drawn token under the warped distribution).  output_logits: the raw logits of every step;
+        output_scores: those logits after MinLength and temperature (the top-k / top-p filters are applied inside the selection kernel and
+        are NOT reflected there).  Both go through the parity capture (eager launches, same ids)."""
+        if num_beams > 1:
+            raise ValueError("`do_sample=True` with `num_beams` > 1 (beam-sample) is not built; use num_return_sequences for several samples.")
+        temperature = kw.pop("temperature", None)
+        temperature = 1.0 if temperature is None else float(temperature)
+        top_k, top_p = kw.pop("top_k", None), kw.pop("top_p", None)
+        seed, stream_ids = kw.pop("seed", None), kw.pop("stream_ids", None)
+        if top_k is None:
+            top_k = getattr(getattr(self, "generation_config", None), "top_k", None)
+            top_k = 50 if top_k is None else top_k
+        top_p = 1.0 if top_p is None else float(top_p)
+        if not temperature > 0.0:
+            raise ValueError(f"`temperature` has to be a strictly positive float, got {temperature}")
+        if int(top_k) < 0:
+            raise ValueError(f"`top_k` has to be a non-negative integer (0 = off), got {top_k}")
+        if not 0.0 < top_p <= 1.0:
+            raise ValueError(f"`top_p` has to be a float > 0 and <= 1, got {top_p}")
+        if num_return < 1:
+            raise ValueError(f"`num_return_sequences` has to be >= 1, got {num_return}")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        self._check_e1(e1)
+        eng = self._eng()
+        max_length = int(max_length or self.config.max_length)
+        attention_mask = self._default_mask(input_ids, attention_mask)
+        skw = dict(max_length=max_length, min_length=int(min_length), temperature=temperature, top_k=int(top_k), top_p=top_p, seed=int(seed),
+                   num_return=num_return, stream_ids=stream_ids, e1=e1)
+        if not as_dict:
+            return eng.generate_sampled(input_ids, bbox, attention_mask, pixel_values, **skw)[0]
+        cap = None
+        if want_scores or want_logits:
+            cap = eng.debug_decode_capture(max_length - 1, int(input_ids.shape[0]) * num_return)
+        try:
+            ids, _, ts = eng.generate_sampled(input_ids, bbox, attention_mask, pixel_values, return_scores=True, **skw)
+        finally:
+            if cap is not None:
+                eng.debug_decode_capture()
+        out = GenerateOutput(sequences=ids, token_scores=ts)
+        if cap is not None:
+            steps = int(ids.shape[1]) - 1
+            raw = cap[:steps]
+            if want_logits:
+                out.logits = tuple(raw[t].clone() for t in range(steps))
+            if want_scores:
+                sc = raw.clone()
+                for t in range(min(steps, max(0, int(min_length) - 1))):
+                    sc[t, :, self.config.eos_token_id] = -float("inf")
+                out.scores = tuple(sc[t] / temperature for t in range(steps))
+        return out
+
     @torch.no_grad()
     def generate(self, input_ids=None, bbox=None, pixel_values=None, attention_mask=None, labels=None, num_beams=1,
                  max_length=None, min_length=0, length_penalty=1.0, early_stopping=False, do_sample=False, e1=None, **kw):
         """ref call: utils_evaluation.py:269-285 (`labels` arrives as a stray kwarg and is ignored).  Without an
         attention_mask the fork's transformers 4.34 base infers one from pad tokens (all ones at the reference's batch
         size 1), which is what is reproduced here; pass a mask explicitly for padded batches."""
-        if do_sample:
-            raise NotImplementedError("sampling is not part of the reference's decode path")
         num_return = int(kw.pop("num_return_sequences", None) or 1)
         as_dict = bool(kw.pop("return_dict_in_generate", False))
         want_scores, want_logits = bool(kw.pop("output_scores", False)), bool(kw.pop("output_logits", False))
         num_beams = int(num_beams)
+        if do_sample:
+            return self._generate_sampled(input_ids, bbox, pixel_values, attention_mask, num_beams, max_length, min_length, e1, num_return,
+                                          as_dict, want_scores, want_logits, kw)
         if num_beams == 1 and num_return > 1:
             raise ValueError(f"Greedy methods without beam search do not support `num_return_sequences` different than 1 (got {num_return}).")
         if num_return > num_beams:
@@ -427,12 +497,7 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
         self._check_e1(e1)
         eng = self._eng()
         max_length = int(max_length or self.config.max_length)
-        if attention_mask is None:
-            pad, eos = self.config.pad_token_id, self.config.eos_token_id
-            if pad is not None and pad != eos and bool((input_ids == pad).any()):
-                attention_mask = (input_ids != pad).long()
-            else:
-                attention_mask = torch.ones_like(input_ids)
+        attention_mask = self._default_mask(input_ids, attention_mask)
         gkw = dict(num_beams=num_beams, max_length=max_length, min_length=int(min_length), length_penalty=float(length_penalty),
                    early_stopping=early_stopping, e1=e1)
         if not as_dict:

@@ -206,6 +206,9 @@ void glds16(const void* gsrc_lane, void* lds_wave_base) {
     memcpy((char*)lds_wave_base + lane * 16, gsrc_lane, 16);
 }
 
+static long g_workgroups = 0;      // workgroups executed since the library was loaded (tests: how much work a call launched)
+extern "C" long emu_workgroups_launched() { return g_workgroups; }
+
 void launch(Dim3 grid, Dim3 block, size_t shmem, const std::function<void()>& body) {
     int nthreads = block.x * block.y * block.z;
     if (nthreads <= 0 || nthreads > 1024) { fprintf(stderr, "emu: bad block size %d\n", nthreads); abort(); }
@@ -215,6 +218,7 @@ void launch(Dim3 grid, Dim3 block, size_t shmem, const std::function<void()>& bo
     for (unsigned bz = 0; bz < grid.z; ++bz)
     for (unsigned by = 0; by < grid.y; ++by)
     for (unsigned bx = 0; bx < grid.x; ++bx) {
+        ++g_workgroups;
         B.fibers.assign(nthreads, Fiber());
         B.waves.assign((nthreads + 63) / 64, Wave());
         for (size_t wv = 0; wv < B.waves.size(); ++wv)
