@@ -2,6 +2,7 @@
 // carving, the VTL encoder, the teacher-forced decoder, and the KV-cached greedy / beam-search generate loop.
 // Host code only orchestrates launches on the caller's stream; every byte of model arithmetic runs in HIP kernels.
 #include "mg_kernels.h"
+#include "mg_graph.h"
 #include "../../include/mgrapher.h"
 
 #include <math.h>
@@ -49,38 +50,33 @@ struct DecLayer { size_t wqkv, wo, ln0, xq, xkv, xo, ln1, wi, wo2, ln2, xq2, wi2
 
 }  // namespace
 
-// A captured decode step.  Every step-dependent value (cache position, key count, output column) is read from the
-// device step counter, so one executable graph serves all steps of a call — and later calls with the same buffers.
-struct StepGraph {
-    struct Key {
-        const void *ws, *out_ids, *top2, *stream;
-        int B, L, K, max_length, min_length, early_stopping, M_e1;
-        float length_penalty;
-        const void* scores;      // beam queue: beam_slot_end_kernel holds the out_scores pointer (NULL or a buffer) inside the captured launch
-        // scored calls (mg_gen_opts): the selection / slot-end launches hold the token-score and beam-index pointers and the n-best count
-        const void *token_scores, *beam_indices;
-        int num_return;
-        // sampled calls (mg_sample_opts): the selection launch holds every one of these by value (temperature 0 = not a sampled call)
-        float temperature, top_p;
-        int top_k;
-        uint64_t seed;
-        const void* stream_ids;
-        bool operator==(const Key& o) const {
-            return ws == o.ws && out_ids == o.out_ids && top2 == o.top2 && stream == o.stream && B == o.B && L == o.L && K == o.K && M_e1 == o.M_e1 &&
-                   max_length == o.max_length && min_length == o.min_length && early_stopping == o.early_stopping &&
-                   length_penalty == o.length_penalty && scores == o.scores && token_scores == o.token_scores &&
-                   beam_indices == o.beam_indices && num_return == o.num_return && temperature == o.temperature && top_p == o.top_p &&
-                   top_k == o.top_k && seed == o.seed && stream_ids == o.stream_ids;
-        }
-    };
-    Key key{};
-    bool valid = false;
-#ifndef MG_EMU
-    hipGraphExec_t exec = nullptr;
-    void reset() { if (exec) (void)hipGraphExecDestroy(exec); exec = nullptr; valid = false; }
-#else
-    void reset() { valid = false; }
-#endif
+// The captured decode steps (mg_graph.h).  Every step-dependent value (cache position, key count, output column) is read from the
+// device step counter or the slot table, so one executable graph serves all steps of a call - and later calls whose key is equal.
+// A key names everything the captured launches hold by value.
+struct BatchStepKey {        // mg_generate / mg_generate_sampled
+    const void *ws, *out_ids, *step_top2, *stream;
+    int B, L, K, max_length, min_length, early_stopping, M_e1;
+    float length_penalty;
+    const void* token_scores;      // greedy scored and sampled calls: the selection launch writes the token log-probabilities
+    // sampled calls (mg_sample_opts): the selection launch holds every one of these (not a sampled call: num_return 1, the rest 0)
+    int num_return, top_k;
+    float temperature, top_p;
+    uint64_t seed;
+    const void* stream_ids;
+    MG_KEY_MEMBERS(BatchStepKey, ws, out_ids, step_top2, stream, B, L, K, max_length, min_length, early_stopping, M_e1, length_penalty,
+                   token_scores, num_return, top_k, temperature, top_p, seed, stream_ids)
+};
+struct QueueStepKey {        // mg_generate_stream*: greedy and beam queues
+    const void *ws, *out_ids, *out_len, *stream;
+    int N, L, chunk, slots, pool_chunks, num_beams, max_length, min_length;
+    bool early_stopping;
+    float length_penalty;
+    // the slot-end launch of the beam queue holds the output pointers (null or a buffer) and the n-best count; the greedy selection the
+    // token-score pointer
+    const void *out_scores, *token_scores, *beam_indices;
+    int num_return;
+    MG_KEY_MEMBERS(QueueStepKey, ws, out_ids, out_len, stream, N, L, chunk, slots, pool_chunks, num_beams, max_length, min_length,
+                   early_stopping, length_penalty, out_scores, token_scores, beam_indices, num_return)
 };
 
 struct mg_model {
@@ -107,9 +103,13 @@ struct mg_model {
     double prof_empty_ms = 0.0;   // summed duration of the empty event brackets recorded right after each timed launch
     long prof_n = 0;
     double prof_keys = 0.0;   // sum over timed launches of the number of (image, key) pairs streamed
-    // one decode step captured as a HIP graph (greedy and beam); replayed while its key matches the call
     size_t fin_a = 0, fin_b = 0, fin_c = 0;
-    StepGraph step_graph;
+    // one decode step captured as a HIP graph (greedy and beam); replayed while its key matches the call.  These three clean up after
+    // themselves, after ~mg_model's body and in reverse order of declaration: the graphs go before the stream they were captured on.
+    NullStreamFork fork;                            // where a call on the null stream runs its decode phase
+    CapturedStep<BatchStepKey> step_graph;
+    CapturedStep<QueueStepKey> stream_graph;        // continuous decoding (mg_generate_stream)
+    void reset_step_graphs() { step_graph.reset(); stream_graph.reset(); }
     std::vector<float> beam_div_host;
     int use_graph = 1;
     bool graph_active = false;
@@ -133,7 +133,6 @@ struct mg_model {
     int dbg_steps = 0;
     const int64_t* dbg_forced = nullptr;
     // continuous decoding (mg_generate_stream): the encoder runs ahead on its own stream
-    StepGraph stream_graph;
     int* stream_host = nullptr;          // pinned read-back ring of the stream counters
     int enc_mode = 1;                    // 0: encoder on the caller's stream (no overlap); 1: own low-priority stream; 2: own stream restricted to enc_mask
     std::vector<uint32_t> enc_mask;
@@ -159,23 +158,13 @@ struct mg_model {
     // OCSR vision branch (mg_attach_e1, swin.hip): calls that pass no precomputed e1 evaluate it from pixel_values themselves
     const mg_e1_model* e1m = nullptr;
     int e1_M = 0;              // its tokens per image
-#ifndef MG_EMU
-    hipStream_t own_stream = nullptr;
-    hipEvent_t fork_ev = nullptr;
-#endif
     ~mg_model() {
-        step_graph.reset();
-        stream_graph.reset();
         if (stream_host) mg_host_free(stream_host);
         if (enc_stream_ready && enc_stream) mg_stream_destroy(enc_stream);
         for (mgEvent_t e : chunk_ev) mg_event_destroy(e);
         for (mgEvent_t e : rb_ev) mg_event_destroy(e);
         for (mgEvent_t e : pace_ev) mg_event_destroy(e);
         if (start_ev) mg_event_destroy(start_ev);
-#ifndef MG_EMU
-        if (own_stream) (void)hipStreamDestroy(own_stream);
-        if (fork_ev) (void)hipEventDestroy(fork_ev);
-#endif
         for (mgEvent_t e : phase_ev) if (e) mg_event_destroy(e);
     }
 
@@ -278,6 +267,37 @@ __global__ __launch_bounds__(256) void copy_bytes_rows_kernel(const uint8_t* src
 }
 
 // ---- workspace -------------------------------------------------------------------------------------------
+// Buffers of the decode rows and of the cross-attention they read: carved once (carve_decode) for the batch call and the queue,
+// and the part of DecodeCtx a call takes over from its workspace as it is.
+struct DecodeBufs {
+    uint16_t *xk, *xv;        // cross K/V: [layer][owner][H][Sx_cap][64]
+    // absorbed form (encx non-null, xk / xv null): the attended encoder states [owner][Sx_cap][d] + the scratch of the three launches:
+    // q' [rows][H][d], context partials
+    uint16_t *encx, *qx, *xpart;
+    float *xml;
+    uint16_t *sk, *sv;        // self-attention caches [layer][row][H][T_cap][64]
+    uint16_t *dq, *dx_pk, *dy_pk;
+    uint16_t *xa, *xb;        // packed [rows][d + inner] operand windows of the pair projections: [bf16(h) | attention context]
+    float *dh, *logits, *rs_part, *rs_part1, *rs_part2;
+    float4* ptop;             // fused greedy tail: per-workgroup top-2 partials of the lm_head launch [rows][V/32] (null: separate embed / selection launches)
+    float* stopv;             // [rows][4] logits of the stop tokens
+    float* kpart;             // K-slab projections with several row tiles: partial sums [16][rows padded][<= ldmax], and their arrival counters
+    int* tickets;             // (zero between launches)
+    int64_t* next_ids;
+    int *unfinished, *anc, *beam_idx;
+    float* beam_div;          // [T_cap + 1] length-penalty divisor per cur_len
+    void* beam_state;
+};
+// What sizes them.  Batch call: `owners` = `groups` = images.  Queue: `owners` = pool entries, `groups` = slots (of K rows each).
+struct DecodeGeom {
+    int owners, groups, K;
+    int form_K;               // the cross-attention form (absorbed or K / V) is chosen as for form_K rows per image (sampled calls: K = samples
+                              // per image for the row counts, form_K = 1 - their rows are greedy rows)
+    int Sx_cap, max_len;
+    bool queue;               // the queue has no fused tail and takes the beam buffers only for beams; the batch call always takes both
+                              // (a sampled call keeps its row -> owner map in anc)
+};
+
 struct Ws {
     // encoder
     uint16_t *xim, *x_pk, *q_pk, *k_pk, *vt_pk, *ctx_pk, *y_pk, *enc_pk, *bidx;
@@ -294,21 +314,7 @@ struct Ws {
     float* e1_f32;            // attached e1 branch: its output [B][M][d] and its workspace
     char* e1_ws;
     size_t e1_ws_bytes;
-    // decode (generate)
-    uint16_t *xk, *xv, *sk, *sv, *dq, *dx_pk, *dy_pk;
-    // weight-absorbed cross-attention (greedy): the states the decoder attends [B][Sx_cap][d], q' [rows][H][d], context partials
-    uint16_t *encx, *qx, *xpart;
-    float *xml;
-    uint16_t *xa, *xb;        // packed [rows][d + inner] operand windows of the pair projections: [bf16(h) | attention context]
-    float *dh, *logits, *slabs, *rs_part, *rs_part1, *rs_part2;
-    float4* ptop;             // fused greedy tail: per-workgroup top-2 partials of the lm_head launch [rows][V/32]
-    float* stopv;             // [rows][4] logits of the stop tokens
-    size_t slab_stride;
-    int* tickets;             // arrival counters of the K-slab projections (zero between launches)
-    int64_t* next_ids;
-    int *unfinished, *anc, *beam_idx;
-    float* beam_div;          // [T_cap + 1] length-penalty divisor per cur_len
-    void* beam_state;
+    DecodeBufs dec;           // generate
     // teacher-forced decoder
     int64_t* tf_ids;
     uint8_t* tf_mask;
@@ -329,11 +335,55 @@ struct Carver {
     }
 };
 
-// form_K > 0: the cross-attention form (absorbed or K / V) is chosen as for form_K rows per image instead of K (sampled calls: K = samples
-// per image for the row counts, form_K = 1 - their rows are greedy rows)
+void carve_decode(const mg_model* m, Carver& c, const DecodeGeom& g, DecodeBufs* b) {
+    const int d = m->d, inner = m->inner, H = m->H, Sx_cap = g.Sx_cap;
+    const int R = g.groups * g.K, Rp = round_up(R, 32);
+    const size_t nl = m->dec.size(), owners = (size_t)g.owners;
+    *b = DecodeBufs{};
+    if (use_absorb(m, g.form_K, R)) {
+        b->encx = c.take<uint16_t>(owners * Sx_cap * d);
+        b->qx = c.take<uint16_t>((size_t)Rp * H * d);
+        b->xpart = c.take<uint16_t>((size_t)Rp * xa_nsplit(m, g.form_K) * H * d);
+        b->xml = c.take<float>((size_t)Rp * xa_nsplit(m, g.form_K) * H * 2);
+    } else {
+        b->xk = c.take<uint16_t>(nl * owners * H * Sx_cap * 64);
+        b->xv = c.take<uint16_t>(nl * owners * H * Sx_cap * 64);
+    }
+    b->sk = c.take<uint16_t>(nl * R * H * (size_t)m->T_cap * 64);
+    b->sv = c.take<uint16_t>(nl * R * H * (size_t)m->T_cap * 64);
+    b->dq = c.take<uint16_t>((size_t)Rp * inner);
+    b->dx_pk = c.take<uint16_t>((size_t)Rp * d);
+    b->dy_pk = c.take<uint16_t>((size_t)Rp * m->dff);
+    b->dh = c.take<float>((size_t)Rp * d);
+    b->logits = c.take<float>((size_t)Rp * round_up(m->V, 32));
+    if (!g.queue) {
+        b->ptop = c.take<float4>((size_t)Rp * (round_up(m->V, 32) / 32));
+        b->stopv = c.take<float>((size_t)Rp * 4);
+    }
+    int ldmax = 3 * inner;
+    if (m->dff > ldmax) ldmax = m->dff;
+    if (d > ldmax) ldmax = d;
+    b->kpart = c.take<float>((size_t)16 * Rp * ldmax);
+    b->tickets = c.take<int>(512);
+    b->rs_part = c.take<float>((size_t)Rp * (d / 8));
+    b->rs_part1 = c.take<float>((size_t)Rp * (d / 8));
+    b->rs_part2 = c.take<float>((size_t)Rp * (d / 8));
+    b->xa = c.take<uint16_t>((size_t)Rp * (d + inner));
+    b->xb = c.take<uint16_t>((size_t)Rp * (d + inner));
+    b->next_ids = c.take<int64_t>(Rp);
+    b->unfinished = c.take<int>(Rp);
+    if (!g.queue || g.K > 1) {
+        b->anc = c.take<int>((size_t)m->T_cap * R);
+        b->beam_idx = c.take<int>(Rp);
+        b->beam_div = c.take<float>((size_t)m->T_cap + 1);
+        b->beam_state = c.take<char>(g.K > 1 ? beam_state_bytes(g.groups, g.K, g.max_len) : 16);
+    }
+}
+
+// form_K > 0: the cross-attention form is chosen as for form_K rows per image instead of K (DecodeGeom::form_K)
 void carve(const mg_model* m, char* base, int B, int L, int K, int max_len, int T, int Me1, Ws* w, int form_K = 0) {
     Carver c{base};
-    const int d = m->d, inner = m->inner, H = m->H;
+    const int d = m->d, inner = m->inner;
     const int S_cap = round_up(L + m->P, 64);
     const int M64 = Me1 > 0 ? round_up(Me1, 64) : 0, Sx_cap = S_cap + M64;      // cross-attention keys: [e1 | encoder]
     const size_t M = (size_t)B * S_cap;
@@ -375,49 +425,7 @@ void carve(const mg_model* m, char* base, int B, int L, int K, int max_len, int 
         (void)mg_e1_workspace_bytes(m->e1m, B, &w->e1_ws_bytes);
         w->e1_ws = c.take<char>(w->e1_ws_bytes);
     }
-    if (max_len > 0) {
-        const int R = B * K, Rp = round_up(R, 32);
-        const size_t nl = m->dec.size();
-        w->xk = w->xv = w->encx = w->qx = w->xpart = nullptr; w->xml = nullptr;
-        const int fK = form_K > 0 ? form_K : K;
-        if (use_absorb(m, fK, R)) {
-            w->encx = c.take<uint16_t>((size_t)B * Sx_cap * d);
-            w->qx = c.take<uint16_t>((size_t)Rp * H * d);
-            w->xpart = c.take<uint16_t>((size_t)Rp * xa_nsplit(m, fK) * H * d);
-            w->xml = c.take<float>((size_t)Rp * xa_nsplit(m, fK) * H * 2);
-        } else {
-            w->xk = c.take<uint16_t>(nl * B * H * Sx_cap * 64);
-            w->xv = c.take<uint16_t>(nl * B * H * Sx_cap * 64);
-        }
-        w->sk = c.take<uint16_t>(nl * R * H * (size_t)m->T_cap * 64);
-        w->sv = c.take<uint16_t>(nl * R * H * (size_t)m->T_cap * 64);
-        w->dq = c.take<uint16_t>((size_t)Rp * inner);
-        w->dx_pk = c.take<uint16_t>((size_t)Rp * d);
-        w->dy_pk = c.take<uint16_t>((size_t)Rp * m->dff);
-        w->dh = c.take<float>((size_t)Rp * d);
-        w->logits = c.take<float>((size_t)Rp * round_up(m->V, 32));
-        w->ptop = c.take<float4>((size_t)Rp * (round_up(m->V, 32) / 32));
-        w->stopv = c.take<float>((size_t)Rp * 4);
-        {
-            int ldmax = 3 * inner;
-            if (m->dff > ldmax) ldmax = m->dff;
-            if (d > ldmax) ldmax = d;
-            w->slab_stride = (size_t)Rp * ldmax;
-            w->slabs = c.take<float>(16 * w->slab_stride);
-            w->tickets = c.take<int>(512);
-            w->rs_part = c.take<float>((size_t)Rp * (d / 8));
-            w->rs_part1 = c.take<float>((size_t)Rp * (d / 8));
-            w->rs_part2 = c.take<float>((size_t)Rp * (d / 8));
-            w->xa = c.take<uint16_t>((size_t)Rp * (d + inner));
-            w->xb = c.take<uint16_t>((size_t)Rp * (d + inner));
-        }
-        w->next_ids = c.take<int64_t>(Rp);
-        w->unfinished = c.take<int>(Rp);
-        w->anc = c.take<int>((size_t)m->T_cap * R);
-        w->beam_idx = c.take<int>(Rp);
-        w->beam_div = c.take<float>((size_t)m->T_cap + 1);
-        w->beam_state = c.take<char>(K > 1 ? beam_state_bytes(B, K, max_len) : 16);
-    }
+    if (max_len > 0) carve_decode(m, c, DecodeGeom{B, B, K, form_K > 0 ? form_K : K, Sx_cap, max_len, false}, &w->dec);
     if (T > 0) {
         const int T_cap = round_up(T, 64);
         const size_t MT = (size_t)B * T_cap;
@@ -444,64 +452,22 @@ void carve(const mg_model* m, char* base, int B, int L, int K, int max_len, int 
 // (every image below it has finished: its pool entry may be overwritten), [8] N
 struct StreamWs {
     Ws enc;                   // encoder workspace of one chunk
-    uint16_t *xk, *xv;        // K/V pool [layer][pool entry][H][Sx_cap][64]  (absorbed form: null; encx = pool of encoder states [pool entry][Sx_cap][d])
-    uint16_t *encx, *qx, *xpart;
-    float *xml;
+    DecodeBufs dec;           // decode rows; cross K/V as a pool [layer][pool entry][H][Sx_cap][64] (absorbed form: pool of encoder states [pool entry][Sx_cap][d])
     size_t pool_stride;       // elements between layers
     int* xlen_pool;           // [pool entries]
-    uint16_t *sk, *sv, *dq, *dx_pk, *dy_pk, *xa, *xb;
-    float *dh, *logits, *rs_part, *rs_part1, *rs_part2, *kpart;
-    int* tickets;
-    int64_t* next_ids;
-    int *unfinished, *pos, *img, *pool, *ctr, *err;
-    // beam queue form (K > 1): `slots` image slots of K rows each; per-slot K/V owner, slot -> image assignment of the step, ancestor
-    // table, beam bookkeeping of the slots
-    int *bpool, *assign, *anc, *beam_idx;
-    float* beam_div;
-    void* beam_state;
+    int *pos, *img, *pool, *ctr, *err;
+    int *bpool, *assign;      // beam queue form (K > 1): `slots` image slots of K rows each; per-slot K/V owner, slot -> image assignment of the step
     size_t total;
 };
 void carve_stream(const mg_model* m, char* base, int chunk, int L, int slots_img, int pool_chunks, StreamWs* w, int K = 1, int max_len = 0) {
     carve(m, base, chunk, L, 1, 0, 0, m->e1_M, &w->enc);
     Carver c{base};
     c.off = w->enc.total;
-    const int d = m->d, inner = m->inner, H = m->H;
-    const int slots = slots_img * K;                        // decode rows
-    const int Sx_cap = round_up(L + m->P, 64) + round_up(m->e1_M, 64), Rp = round_up(slots, 32);      // keys of an image: [e1 tokens | encoder positions]
-    const size_t nl = m->dec.size(), entries = (size_t)pool_chunks * chunk;
-    w->pool_stride = entries * H * Sx_cap * 64;
-    w->xk = w->xv = w->encx = w->qx = w->xpart = nullptr; w->xml = nullptr;
-    if (use_absorb(m, K, slots)) {
-        w->encx = c.take<uint16_t>(entries * Sx_cap * d);
-        w->qx = c.take<uint16_t>((size_t)Rp * H * d);
-        w->xpart = c.take<uint16_t>((size_t)Rp * xa_nsplit(m, K) * H * d);
-        w->xml = c.take<float>((size_t)Rp * xa_nsplit(m, K) * H * 2);
-    } else {
-        w->xk = c.take<uint16_t>(nl * w->pool_stride);
-        w->xv = c.take<uint16_t>(nl * w->pool_stride);
-    }
+    const int Sx_cap = round_up(L + m->P, 64) + round_up(m->e1_M, 64);      // keys of an image: [e1 tokens | encoder positions]
+    const int entries = pool_chunks * chunk, Rp = round_up(slots_img * K, 32);
+    w->pool_stride = (size_t)entries * m->H * Sx_cap * 64;
+    carve_decode(m, c, DecodeGeom{entries, slots_img, K, K, Sx_cap, max_len, true}, &w->dec);
     w->xlen_pool = c.take<int>(entries);
-    w->sk = c.take<uint16_t>(nl * slots * H * (size_t)m->T_cap * 64);
-    w->sv = c.take<uint16_t>(nl * slots * H * (size_t)m->T_cap * 64);
-    w->dq = c.take<uint16_t>((size_t)Rp * inner);
-    w->dx_pk = c.take<uint16_t>((size_t)Rp * d);
-    w->dy_pk = c.take<uint16_t>((size_t)Rp * m->dff);
-    w->dh = c.take<float>((size_t)Rp * d);
-    w->logits = c.take<float>((size_t)Rp * round_up(m->V, 32));
-    w->rs_part = c.take<float>((size_t)Rp * (d / 8));
-    w->rs_part1 = c.take<float>((size_t)Rp * (d / 8));
-    w->rs_part2 = c.take<float>((size_t)Rp * (d / 8));
-    w->xa = c.take<uint16_t>((size_t)Rp * (d + inner));
-    w->xb = c.take<uint16_t>((size_t)Rp * (d + inner));
-    {
-        int ldmax = 3 * inner;
-        if (m->dff > ldmax) ldmax = m->dff;
-        if (d > ldmax) ldmax = d;
-        w->kpart = c.take<float>((size_t)16 * Rp * ldmax);
-        w->tickets = c.take<int>(512);
-    }
-    w->next_ids = c.take<int64_t>(Rp);
-    w->unfinished = c.take<int>(Rp);
     w->pos = c.take<int>(Rp);
     w->img = c.take<int>(Rp);
     w->pool = c.take<int>(Rp);
@@ -509,14 +475,6 @@ void carve_stream(const mg_model* m, char* base, int chunk, int L, int slots_img
     w->err = c.take<int>(64);
     w->bpool = c.take<int>(round_up(slots_img, 32));
     w->assign = c.take<int>(round_up(slots_img, 32));
-    if (K > 1) {
-        w->anc = c.take<int>((size_t)m->T_cap * slots);
-        w->beam_idx = c.take<int>(Rp);
-        w->beam_div = c.take<float>((size_t)m->T_cap + 1);
-        w->beam_state = c.take<char>(beam_state_bytes(slots_img, K, max_len));
-    } else {
-        w->anc = nullptr; w->beam_idx = nullptr; w->beam_div = nullptr; w->beam_state = nullptr;
-    }
     w->total = align_up(c.off, 256);
 }
 __global__ __launch_bounds__(256) void stream_init_kernel(int64_t* out_ids, int* out_len, int N, int max_len, int64_t start, int64_t pad,
@@ -606,31 +564,67 @@ void ffn_block(const mg_model* m, bool rows_mode, float* hidden, uint16_t* x_pk,
     rows_mode ? gemm_rows(b, EPI_F32_RESID, st) : gemm(b, EPI_F32_RESID, st);
 }
 
+// Cross-attention keys of the `n` images whose encoder pass left `we`, into owners [owner0, owner0 + n) of the decode buffers, once per
+// image (stock:524-538) and compacted to attended positions.  The e1 tokens (if any: M64 rows) come first in an image's stream, the
+// attended encoder positions follow (xrow carries the offset) - cross-attention has no positional term, so the order of the keys is
+// immaterial.  Absorbed form (k_xattn.hip): the decoder layers stream the attended states themselves - one compaction instead of
+// 2 x N_dec projections.
+void prepare_cross_kv(const mg_model* m, const Ws& we, int n, const DecodeBufs& b, size_t layer_stride, int owner0, int Sx_cap, int M64,
+                      mgStream_t st) {
+    const int d = m->d, H = m->H, inner = m->inner, S_cap = Sx_cap - M64;
+    if (b.encx) {
+        uint16_t* ex = b.encx + (size_t)owner0 * Sx_cap * d;
+        if (M64) enc_rows(we.e1_pk, we.e1_map, ex, n, M64, Sx_cap, d, st);
+        enc_rows(we.enc_pk, we.xrow, ex, n, S_cap, Sx_cap, d, st);
+        enc_pad_rows(ex, we.xlen, n, Sx_cap, d, st);
+        return;
+    }
+    const size_t off = (size_t)owner0 * H * Sx_cap * 64;
+    for (size_t li = 0; li < m->dec.size(); ++li) {
+        uint16_t *xk = b.xk + li * layer_stride + off, *xv = b.xv + li * layer_stride + off;
+        if (M64) {
+            GemmArgs ke = gemm_args(we.e1_pk, m->at<uint16_t>(m->dec[li].xkv), n * M64, 2 * inner, d);
+            set_heads(ke, H, M64, Sx_cap, xk, HF_NATURAL, xv, HF_NATURAL, nullptr, HF_NONE);
+            ke.heads.row_map = we.e1_map;
+            gemm(ke, EPI_HEADS, st);
+        }
+        GemmArgs kv = gemm_args(we.enc_pk, m->at<uint16_t>(m->dec[li].xkv), n * S_cap, 2 * inner, d);
+        set_heads(kv, H, S_cap, Sx_cap, xk, HF_NATURAL, xv, HF_NATURAL, nullptr, HF_NONE);
+        kv.heads.row_map = we.xrow;
+        if (m->st_row_tiles) { kv.row_tiles = we.row_tiles + 1; kv.n_row_tiles = we.row_tiles; }      // left by mg_encode
+        gemm(kv, EPI_HEADS, st);
+    }
+}
+
+// beam search: the length-penalty divisor per cur_len.  The host vector may be resized by the context's next call: a caller that
+// does not end with a host synchronisation of st synchronises after this.
+void upload_beam_div(mg_model* m, float* beam_div, int max_length, float length_penalty, mgStream_t st) {
+    m->beam_div_host.resize((size_t)max_length + 1);
+    for (int c = 0; c <= max_length; ++c) m->beam_div_host[c] = beam_length_divisor(c, length_penalty);
+    mg_memcpy_async(beam_div, m->beam_div_host.data(), m->beam_div_host.size() * sizeof(float), st);
+}
+
+// cross-attention brackets of the call's timed steps (decode_step) into the running totals; keys = (image, key) pairs a launch streamed
+void accumulate_cross_profile(mg_model* m, double keys) {
+    for (size_t i = 0; i + 2 < m->prof_used; i += 3) {
+        m->prof_ms += mg_event_elapsed_ms(m->prof_ev[i], m->prof_ev[i + 1]);
+        m->prof_empty_ms += mg_event_elapsed_ms(m->prof_ev[i + 1], m->prof_ev[i + 2]);
+        m->prof_n += 1;
+        m->prof_keys += keys;
+    }
+    m->prof_used = 0;
+}
+
 }  // namespace
 
 // Everything one decode step needs besides the model: the buffers of the live rows, the cross K/V streams they read and the
 // selection state.  Two users: mg_generate (one batch, all rows at the same position) and mg_generate_stream (continuous
 // decoding: `slots.pos` non-null, every row at its own position on its own image, K/V streams in a pool).
-struct DecodeCtx {
-    uint16_t *xk, *xv;        // cross K/V: [layer][owner][H][Sx_cap][64]
-    // absorbed form (encx non-null): the attended encoder states [owner][Sx_cap][d] + the scratch of the three launches
-    uint16_t *encx, *qx, *xpart;
-    float *xml;
-    size_t xkv_stride;        // elements between layers
+struct DecodeCtx : DecodeBufs {
+    size_t xkv_stride;        // cross K/V: elements between layers
     int Sx_cap;
     const int* xlen;          // keys per K/V owner
-    uint16_t *sk, *sv;        // self-attention caches [layer][row][H][T_cap][64]
-    size_t skv_stride;
-    uint16_t *dq, *dx_pk, *dy_pk, *xa, *xb;
-    float *dh, *logits, *rs_part, *rs_part1, *rs_part2;
-    float* kpart;             // K-slab projections with several row tiles: partial sums [16][rows padded][<= ldmax], and their arrival counters
-    int* tickets;
-    float4* ptop;             // fused greedy tail (null: separate embed / selection launches)
-    float* stopv;
-    int64_t* next_ids;
-    int *unfinished, *anc, *beam_idx;
-    float* beam_div;
-    void* beam_state;
+    size_t skv_stride;        // self-attention caches: elements between layers
     int* counters;
     int B, K, R, max_length, min_length, early_stopping;
     float length_penalty;
@@ -1139,7 +1133,7 @@ int mg_finalize(mg_model* m, void* stream) {
 int mg_attach_e1(mg_model* m, const mg_e1_model* e1) {
     if (!m) return fail(MG_E_ARG, "mg_attach_e1: null model");
     MG_ONE_CALL(m, "mg_attach_e1");
-    if (!e1) { m->e1m = nullptr; m->e1_M = 0; m->step_graph.reset(); m->stream_graph.reset(); return MG_OK; }
+    if (!e1) { m->e1m = nullptr; m->e1_M = 0; m->reset_step_graphs(); return MG_OK; }
     int tokens = 0, dm = 0, src = 0, ch = 0, fin = 0;
     e1_info(e1, &tokens, &dm, &src, &ch, &fin);
     if (!fin) return fail(MG_E_STATE, "mg_attach_e1: mg_e1_finalize has not run on the branch");
@@ -1147,7 +1141,7 @@ int mg_attach_e1(mg_model* m, const mg_e1_model* e1) {
         return fail(MG_E_SHAPE, "mg_attach_e1: the branch produces %d features from %d-channel %d px inputs, the model has d_model %d and %d-channel %d px pixel_values",
                     dm, ch, src, m->d, m->c.num_channels, m->c.image_size);
     m->e1m = e1; m->e1_M = tokens;
-    m->step_graph.reset(); m->stream_graph.reset();       // captured steps hold the key-stream geometry of the previous setting
+    m->reset_step_graphs();       // captured steps hold the key-stream geometry of the previous setting
     return MG_OK;
 }
 
@@ -1416,75 +1410,34 @@ static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
     if (m->phase_on) mg_event_record(m->phase_ev[0], st);
     int rc = mg_encode(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, e1, M_in, B, L, nullptr, nullptr);
     if (rc != MG_OK) return rc;
-    const int d = m->d, H = m->H, inner = m->inner, S_cap = m->st_Scap, M = B * S_cap;
+    const int d = m->d, H = m->H, inner = m->inner, S_cap = m->st_Scap;
     const int R = B * K * NS, T_cap = m->T_cap;
-    const size_t nl = m->dec.size();
     const int M64 = M_e1 > 0 ? round_up(M_e1, 64) : 0, Sx_cap = S_cap + M64;
     const size_t xkv_stride = (size_t)B * H * Sx_cap * 64, skv_stride = (size_t)R * H * T_cap * 64;
-    // cross-attention K/V of every decoder layer, once per image (stock:524-538), compacted to attended positions; the
-    // e1 tokens (if any) occupy rows [0, M_e1) of an image's stream, the attended encoder positions follow (xrow carries
-    // the offset) - cross-attention has no positional term, so the order of the keys is immaterial
-    const bool absorbed = use_absorb(m, K, R);
-    if (absorbed) {
-        // weight-absorbed form (k_xattn.hip): the decoder layers stream the attended states themselves - one compaction instead of
-        // 2 x N_dec projections
-        if (M64) enc_rows(w.e1_pk, w.e1_map, w.encx, B, M64, Sx_cap, d, st);
-        enc_rows(w.enc_pk, w.xrow, w.encx, B, S_cap, Sx_cap, d, st);
-        enc_pad_rows(w.encx, w.xlen, B, Sx_cap, d, st);
-    }
-    for (size_t li = 0; li < nl && !absorbed; ++li) {
-        if (M64) {
-            GemmArgs ke = gemm_args(w.e1_pk, m->at<uint16_t>(m->dec[li].xkv), B * M64, 2 * inner, d);
-            set_heads(ke, H, M64, Sx_cap, w.xk + li * xkv_stride, HF_NATURAL, w.xv + li * xkv_stride, HF_NATURAL, nullptr, HF_NONE);
-            ke.heads.row_map = w.e1_map;
-            gemm(ke, EPI_HEADS, st);
-        }
-        GemmArgs kv = gemm_args(w.enc_pk, m->at<uint16_t>(m->dec[li].xkv), M, 2 * inner, d);
-        set_heads(kv, H, S_cap, Sx_cap, w.xk + li * xkv_stride, HF_NATURAL, w.xv + li * xkv_stride, HF_NATURAL, nullptr, HF_NONE);
-        kv.heads.row_map = w.xrow;
-        if (m->st_row_tiles) { kv.row_tiles = w.row_tiles + 1; kv.n_row_tiles = w.row_tiles; }      // left by mg_encode
-        gemm(kv, EPI_HEADS, st);
-    }
+    const DecodeBufs& db = w.dec;
+    prepare_cross_kv(m, w, B, db, xkv_stride, 0, Sx_cap, M64, st);
     if (m->phase_on) mg_event_record(m->phase_ev[1], st);
     int* counters = w.counters;
     const int64_t start = m->c.decoder_start_token_id, pad = m->c.pad_token_id;
-#ifndef MG_EMU
-    // The legacy null stream cannot be captured: the decode phase then runs on a stream the model owns, ordered after
-    // the caller's stream by an event (the call ends with a host synchronisation of that stream, which orders it
-    // before anything the caller enqueues later).
-    if (m->use_graph == 1 && st == nullptr) {
-        if (!m->own_stream && hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking) != hipSuccess) m->own_stream = nullptr;
-        if (!m->fork_ev && hipEventCreateWithFlags(&m->fork_ev, hipEventDisableTiming) != hipSuccess) m->fork_ev = nullptr;
-        if (m->own_stream && m->fork_ev && hipEventRecord(m->fork_ev, st) == hipSuccess &&
-            hipStreamWaitEvent(m->own_stream, m->fork_ev, 0) == hipSuccess)
-            st = m->own_stream;
-    }
-#endif
+    if (m->use_graph == 1) st = m->fork.from(st);      // (a null stream cannot be captured)
     if (K == 1) {
-        MG_LAUNCH(fill_ids_kernel, dim3(R), dim3(64), 0, st, w.next_ids, out_ids, w.unfinished, counters, R, max_length, start, pad);
+        MG_LAUNCH(fill_ids_kernel, dim3(R), dim3(64), 0, st, db.next_ids, out_ids, db.unfinished, counters, R, max_length, start, pad);
     } else {
-        beam_init(w.beam_state, B, K, max_length, (int)pad, m->c.eos_token_id, (int)start, w.next_ids, w.anc, T_cap, counters, st);
-        m->beam_div_host.resize((size_t)max_length + 1);
-        for (int c = 0; c <= max_length; ++c) m->beam_div_host[c] = beam_length_divisor(c, length_penalty);
-        mg_memcpy_async(w.beam_div, m->beam_div_host.data(), m->beam_div_host.size() * sizeof(float), st);
+        beam_init(db.beam_state, B, K, max_length, (int)pad, m->c.eos_token_id, (int)start, db.next_ids, db.anc, T_cap, counters, st);
+        upload_beam_div(m, db.beam_div, max_length, length_penalty, st);
     }
     int steps_done = 0;
     int host_flag[4] = {0, 0, 0, 0};
+    DecodeCtx dc{};
+    static_cast<DecodeBufs&>(dc) = db;
+    dc.xkv_stride = xkv_stride; dc.Sx_cap = Sx_cap; dc.xlen = w.xlen; dc.skv_stride = skv_stride;
+    mg_memset_async(db.tickets, 0, 512 * sizeof(int), st);
+    dc.counters = counters;
+    dc.B = B; dc.K = K; dc.R = R; dc.max_length = max_length; dc.min_length = min_length; dc.early_stopping = early_stopping;
+    dc.length_penalty = length_penalty; dc.out_ids = out_ids; dc.step_top2 = step_top2;
     // greedy with EOS enabled: finished rows emit pad whatever they compute, their attention launches skip them
     // (not under the parity instrumentation, which compares every row's logits at every captured step)
-    const int* live = (K == 1 && min_length < max_length && !m->dbg_logits && !m->dbg_forced) ? w.unfinished : nullptr;
-    DecodeCtx dc{};
-    dc.xk = w.xk; dc.xv = w.xv; dc.xkv_stride = xkv_stride; dc.Sx_cap = Sx_cap; dc.xlen = w.xlen;
-    dc.encx = w.encx; dc.qx = w.qx; dc.xpart = w.xpart; dc.xml = w.xml;
-    dc.sk = w.sk; dc.sv = w.sv; dc.skv_stride = skv_stride;
-    dc.dq = w.dq; dc.dx_pk = w.dx_pk; dc.dy_pk = w.dy_pk; dc.xa = w.xa; dc.xb = w.xb;
-    dc.dh = w.dh; dc.logits = w.logits; dc.rs_part = w.rs_part; dc.rs_part1 = w.rs_part1; dc.rs_part2 = w.rs_part2;
-    dc.kpart = w.slabs; dc.tickets = w.tickets;
-    mg_memset_async(w.tickets, 0, 512 * sizeof(int), st);
-    dc.next_ids = w.next_ids; dc.unfinished = w.unfinished; dc.anc = w.anc; dc.beam_idx = w.beam_idx; dc.beam_div = w.beam_div;
-    dc.beam_state = w.beam_state; dc.counters = counters;
-    dc.B = B; dc.K = K; dc.R = R; dc.max_length = max_length; dc.min_length = min_length; dc.early_stopping = early_stopping;
-    dc.length_penalty = length_penalty; dc.out_ids = out_ids; dc.step_top2 = step_top2; dc.live = live;
+    dc.live = (K == 1 && min_length < max_length && !m->dbg_logits && !m->dbg_forced) ? db.unfinished : nullptr;
     if (K == 1 && token_scores) {      // columns a row does not reach (after its EOS, after the last step) hold 0
         dc.token_scores = token_scores;
         mg_memset_async(token_scores, 0, (size_t)R * (max_length - 1) * sizeof(float), st);
@@ -1492,48 +1445,27 @@ static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
     dc.samp = samp;
     if (samp && NS > 1) {              // (the ancestor table's buffer is free: a sampled call has no beams.  The live-row skip of the attention
                                        // launches is per ROW in both cross-attention forms, so the samples of an image finish independently)
-        MG_LAUNCH(row_owner_kernel, dim3((R + 255) / 256), dim3(256), 0, st, w.anc, R, NS);
-        dc.slots.pool = w.anc;
+        MG_LAUNCH(row_owner_kernel, dim3((R + 255) / 256), dim3(256), 0, st, db.anc, R, NS);
+        dc.slots.pool = db.anc;
     }
     // greedy batch calls run the fused tail (lm_head top-2 partials -> selection + next embedding in one launch); the parity
     // instrumentation needs the full logits / overrides the fed token, and d_model > 2048 would change the norm's summation order
     const bool fused_tail = K == 1 && !samp && m->fused_tail && !m->dbg_logits && !m->dbg_forced && d <= 2048;
-    if (fused_tail) {
-        dc.ptop = w.ptop; dc.stopv = w.stopv;
-        embed_norm_rows(w.next_ids, m->at<uint16_t>(m->tok_emb), w.dh, m->at<float>(m->dec[0].ln0), w.dx_pk, w.xa, d + inner, 0, R, d, m->V,
+    if (fused_tail)
+        embed_norm_rows(db.next_ids, m->at<uint16_t>(m->tok_emb), db.dh, m->at<float>(m->dec[0].ln0), db.dx_pk, db.xa, d + inner, 0, R, d, m->V,
                         counters + 3, m->c.layer_norm_epsilon, st);      // the start token; later steps: greedy_select_fused
-    }
+    else { dc.ptop = nullptr; dc.stopv = nullptr; }      // decode_step takes a non-null ptop as its fused-tail switch
     auto decode_step = [&](int t, const int* tdev, bool time_cross) { ::decode_step(m, dc, t, tdev, time_cross, st); };
     bool graphed = false;
     const bool instrumented = m->dbg_logits || m->dbg_forced;      // by-value eager launches of the same kernels
-#ifndef MG_EMU
     if (m->use_graph == 1 && !instrumented) {
-        const StepGraph::Key key{ws, out_ids, step_top2, (const void*)st, B, L, K, max_length, min_length, early_stopping, M_e1, length_penalty, nullptr,
-                                 dc.token_scores, nullptr, samp ? NS : 1, samp ? samp->temperature : 0.f, samp ? samp->top_p : 0.f,
-                                 samp ? samp->top_k : 0, samp ? samp->seed : 0, samp ? (const void*)samp->stream_ids : nullptr};
-        StepGraph& sg = m->step_graph;
-        if (!(sg.valid && sg.key == key)) {
-            std::lock_guard<std::mutex> capture_lock(mg_capture_mutex());
-            sg.reset();
-            hipGraph_t graph = nullptr;
-            hipError_t e1 = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal), e2 = hipSuccess, e3 = hipSuccess;
-            if (e1 == hipSuccess) {
-                decode_step(0, counters + 2, false);
-                e2 = hipStreamEndCapture(st, &graph);
-                if (e2 == hipSuccess && graph) {
-                    e3 = hipGraphInstantiate(&sg.exec, graph, nullptr, nullptr, 0);
-                    if (e3 == hipSuccess) { sg.key = key; sg.valid = true; }
-                }
-                if (graph) (void)hipGraphDestroy(graph);
-            }
-            if (!sg.valid && getenv("MG_DEBUG"))
-                fprintf(stderr, "%s: decode-step capture failed (begin %s, end %s, instantiate %s); launching eagerly\n", who,
-                        hipGetErrorName(e1), hipGetErrorName(e2), hipGetErrorName(e3));
-            (void)hipGetLastError();
-        }
-        graphed = sg.valid;
+        BatchStepKey key{};
+        key.ws = ws; key.out_ids = out_ids; key.step_top2 = step_top2; key.stream = (const void*)st;
+        key.B = B; key.L = L; key.K = K; key.max_length = max_length; key.min_length = min_length; key.early_stopping = early_stopping;
+        key.M_e1 = M_e1; key.length_penalty = length_penalty; key.token_scores = dc.token_scores; key.num_return = NS;
+        if (samp) { key.top_k = samp->top_k; key.temperature = samp->temperature; key.top_p = samp->top_p; key.seed = samp->seed; key.stream_ids = samp->stream_ids; }
+        graphed = m->step_graph.ensure(key, st, who, [&] { decode_step(0, counters + 2, false); });
     }
-#endif
     m->graph_active = graphed;
     // The host enqueues steps far faster than the GPU runs them; a full runtime queue makes the launching thread SPIN inside the launch
     // call (one busy core per execution context).  Pace it instead: every 8 steps an event is recorded, and before enqueueing further the
@@ -1548,12 +1480,9 @@ static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
             mg_event_record(m->pace_ev[k % PACE_RING], st);
         }
         const bool timed_step = m->prof_every > 0 && (t % m->prof_every) == 0;
-#ifndef MG_EMU
         if (graphed && !timed_step) {
-            if (hipGraphLaunch(m->step_graph.exec, st) != hipSuccess) return fail(MG_E_HIP, "%s: hipGraphLaunch failed", who);
-        } else
-#endif
-        {
+            if (!m->step_graph.launch(st)) return fail(MG_E_HIP, "%s: hipGraphLaunch failed", who);
+        } else {
             // use_graph == 2: the device-counter form launched eagerly (what the graph replays; testable without HIP graphs).
             // A timed step of a graphed call launches that same device-counter form, so the bracketed launches are the
             // kernels the graph replays (the step counter lives on the device and advances identically).
@@ -1572,7 +1501,7 @@ static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
     }
     if (K > 1) {
         const BeamOut nb{num_return, beam_indices, token_scores};
-        beam_finalize(w.beam_state, B, K, max_length, out_ids, counters + 4, opts ? opts->seq_scores : out_scores, st, &nb);
+        beam_finalize(db.beam_state, B, K, max_length, out_ids, counters + 4, opts ? opts->seq_scores : out_scores, st, &nb);
     }
     if (m->phase_on) mg_event_record(m->phase_ev[2], st);
     std::vector<int> xlen_host;
@@ -1586,13 +1515,7 @@ static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
     if (m->prof_used) {
         double keys = 0.0;
         for (int b = 0; b < B; ++b) keys += xlen_host[b];
-        for (size_t i = 0; i + 2 < m->prof_used; i += 3) {
-            m->prof_ms += mg_event_elapsed_ms(m->prof_ev[i], m->prof_ev[i + 1]);
-            m->prof_empty_ms += mg_event_elapsed_ms(m->prof_ev[i + 1], m->prof_ev[i + 2]);
-            m->prof_n += 1;
-            m->prof_keys += keys;
-        }
-        m->prof_used = 0;
+        accumulate_cross_profile(m, keys);
     }
     if (m->phase_on) {
         m->phase_enc_ms += mg_event_elapsed_ms(m->phase_ev[0], m->phase_ev[1]);
@@ -1679,9 +1602,8 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
     carve_stream(m, (char*)ws, chunk, L, slots, pool_chunks, &w, K, max_length);
     if (w.total > ws_bytes) return fail(MG_E_WORKSPACE, "%s: workspace too small (%zu < %zu)", who, ws_bytes, w.total);
     mgStream_t st = (mgStream_t)stream;
-    const int d = m->d, H = m->H, inner = m->inner, P = m->P;
+    const int H = m->H, P = m->P;
     const int S_cap = round_up(L + P, 64), M64 = round_up(m->e1_M, 64), Sx_cap = S_cap + M64;
-    const size_t nl = m->dec.size();
     const int n_chunks = (N + chunk - 1) / chunk;
     const int entries = pool_chunks * chunk;
     const size_t img_in = (size_t)m->c.num_channels * m->c.image_size * m->c.image_size;
@@ -1691,14 +1613,7 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
             return fail(MG_E_HIP, "%s: could not create the encoder stream", who);
         m->enc_stream_ready = true;
     }
-#ifndef MG_EMU
-    if (st == nullptr) {       // the legacy null stream synchronises with every other stream and cannot be captured: own stream
-        if (!m->own_stream && hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking) != hipSuccess) m->own_stream = nullptr;
-        if (!m->fork_ev && hipEventCreateWithFlags(&m->fork_ev, hipEventDisableTiming) != hipSuccess) m->fork_ev = nullptr;
-        if (m->own_stream && m->fork_ev && hipEventRecord(m->fork_ev, st) == hipSuccess && hipStreamWaitEvent(m->own_stream, m->fork_ev, 0) == hipSuccess)
-            st = m->own_stream;
-    }
-#endif
+    st = m->fork.from(st);      // (also without a graph: the null stream would synchronise with the encoder stream)
     mgStream_t es = m->enc_mode == 0 ? st : m->enc_stream;
     while ((int)m->chunk_ev.size() < 2 * pool_chunks + 2) { mgEvent_t e; if (mg_event_create(&e) != 0) return fail(MG_E_HIP, "event"); m->chunk_ev.push_back(e); }
     constexpr int RB = 4, GROUP = 4;          // read-back ring depth, steps per host iteration
@@ -1707,32 +1622,26 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
     if (!m->stream_host && !(m->stream_host = (int*)mg_host_alloc(RB * 16 * sizeof(int)))) return fail(MG_E_HIP, "pinned host buffer");
     // slot table, outputs
     const int64_t start = m->c.decoder_start_token_id, pad = m->c.pad_token_id;
-    MG_LAUNCH(stream_init_kernel, dim3(64), dim3(256), 0, st, out_ids, out_len, N, max_length, start, pad, w.unfinished, w.pos, w.img, w.pool,
-              w.next_ids, R, w.ctr, w.err);
+    const DecodeBufs& db = w.dec;
+    MG_LAUNCH(stream_init_kernel, dim3(64), dim3(256), 0, st, out_ids, out_len, N, max_length, start, pad, db.unfinished, w.pos, w.img, w.pool,
+              db.next_ids, R, w.ctr, w.err);
     mg_memset_async(w.bpool, 0, (size_t)round_up(slots, 32) * sizeof(int), st);
     mg_memset_async(w.assign, 0xFF, (size_t)round_up(slots, 32) * sizeof(int), st);
     mg_memset_async(w.xlen_pool, 0, (size_t)entries * sizeof(int), st);           // (idle slots' cross-attention is skipped; belt and braces)
     if (K > 1) {
-        m->beam_div_host.resize((size_t)max_length + 1);
-        for (int c = 0; c <= max_length; ++c) m->beam_div_host[c] = beam_length_divisor(c, length_penalty);
-        mg_memcpy_async(w.beam_div, m->beam_div_host.data(), m->beam_div_host.size() * sizeof(float), st);
-        mg_stream_sync(st);        // (the host vector may be resized by the context's next call)
+        upload_beam_div(m, db.beam_div, max_length, length_penalty, st);
+        mg_stream_sync(st);
     }
     mg_event_record(m->start_ev, st);
     if (es != st) mg_stream_wait_event(es, m->start_ev);      // inputs / workspace are ordered behind the caller's earlier work
     DecodeCtx dc{};
-    dc.xk = w.xk; dc.xv = w.xv; dc.xkv_stride = w.pool_stride; dc.Sx_cap = Sx_cap; dc.xlen = w.xlen_pool;
-    dc.encx = w.encx; dc.qx = w.qx; dc.xpart = w.xpart; dc.xml = w.xml;
-    dc.sk = w.sk; dc.sv = w.sv; dc.skv_stride = (size_t)R * H * m->T_cap * 64;
-    dc.dq = w.dq; dc.dx_pk = w.dx_pk; dc.dy_pk = w.dy_pk; dc.xa = w.xa; dc.xb = w.xb;
-    dc.dh = w.dh; dc.logits = w.logits; dc.rs_part = w.rs_part; dc.rs_part1 = w.rs_part1; dc.rs_part2 = w.rs_part2;
-    dc.kpart = w.kpart; dc.tickets = w.tickets;
-    mg_memset_async(w.tickets, 0, 512 * sizeof(int), st);
-    dc.next_ids = w.next_ids; dc.unfinished = w.unfinished; dc.counters = w.ctr;
+    static_cast<DecodeBufs&>(dc) = db;
+    dc.xkv_stride = w.pool_stride; dc.Sx_cap = Sx_cap; dc.xlen = w.xlen_pool; dc.skv_stride = (size_t)R * H * m->T_cap * 64;
+    mg_memset_async(db.tickets, 0, 512 * sizeof(int), st);
+    dc.counters = w.ctr;
     dc.B = slots; dc.K = K; dc.R = R; dc.max_length = max_length; dc.min_length = min_length; dc.length_penalty = length_penalty;
     dc.early_stopping = early_stopping;
-    dc.out_ids = out_ids; dc.live = w.unfinished;
-    dc.anc = w.anc; dc.beam_idx = w.beam_idx; dc.beam_div = w.beam_div; dc.beam_state = w.beam_state;
+    dc.out_ids = out_ids; dc.live = db.unfinished;
     dc.bpool = w.bpool; dc.assign = w.assign; dc.out_len = out_len; dc.out_scores = out_scores;
     if (K == 1 && token_scores) {      // columns an image does not reach (after its EOS) hold 0
         dc.token_scores = token_scores;
@@ -1742,28 +1651,14 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
     dc.slots = SlotTable{w.pos, w.img, w.pool, w.ctr, out_len, entries, (int)start};
     // the step as a graph (every step-dependent value lives in the slot table)
     bool graphed = false;
-#ifndef MG_EMU
     if (m->use_graph == 1) {
-        const StepGraph::Key key{ws, out_ids, out_len, (const void*)st, slots * 16 + K, L, chunk, max_length, min_length, N * 2 + (early_stopping ? 1 : 0),
-                                 pool_chunks, length_penalty, (const void*)out_scores, token_scores, dc.nbest.beam_indices, num_return};
-                                 // (B = slots and beams, K = chunk, early_stopping = N and the flag, M_e1 = pool_chunks)
-        StepGraph& sg = m->stream_graph;
-        if (!(sg.valid && sg.key == key)) {
-            std::lock_guard<std::mutex> capture_lock(mg_capture_mutex());
-            sg.reset();
-            hipGraph_t graph = nullptr;
-            if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                decode_step(m, dc, 0, nullptr, false, st);
-                if (hipStreamEndCapture(st, &graph) == hipSuccess && graph && hipGraphInstantiate(&sg.exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-                    sg.key = key; sg.valid = true;
-                }
-                if (graph) (void)hipGraphDestroy(graph);
-            }
-            (void)hipGetLastError();
-        }
-        graphed = sg.valid;
+        QueueStepKey key{};
+        key.ws = ws; key.out_ids = out_ids; key.out_len = out_len; key.stream = (const void*)st;
+        key.N = N; key.L = L; key.chunk = chunk; key.slots = slots; key.pool_chunks = pool_chunks; key.num_beams = K;
+        key.max_length = max_length; key.min_length = min_length; key.early_stopping = early_stopping != 0; key.length_penalty = length_penalty;
+        key.out_scores = out_scores; key.token_scores = token_scores; key.beam_indices = dc.nbest.beam_indices; key.num_return = num_return;
+        graphed = m->stream_graph.ensure(key, st, who, [&] { decode_step(m, dc, 0, nullptr, false, st); });
     }
-#endif
     m->graph_active = graphed;
     int submitted = 0, announced = 0;           // chunks handed to the encoder stream / made visible to the slots
     int oldest_host = 0, done_host = 0, live_host = 0, head_host = 0;
@@ -1780,27 +1675,7 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
         if (rc != MG_OK) return rc;
         Ws we;
         carve(m, (char*)ws, n, L, 1, 0, 0, m->e1_M, &we);         // the chunk's own carving (a short last chunk uses less of the region)
-        const size_t ent_off = (size_t)entry0 * H * Sx_cap * 64;
-        const bool absorbed = w.encx != nullptr;
-        if (absorbed) {        // the chunk's attended states into its pool entries (as mg_generate)
-            uint16_t* ex = w.encx + (size_t)entry0 * Sx_cap * d;
-            if (M64) enc_rows(we.e1_pk, we.e1_map, ex, n, M64, Sx_cap, d, es);
-            enc_rows(we.enc_pk, we.xrow, ex, n, S_cap, Sx_cap, d, es);
-            enc_pad_rows(ex, we.xlen, n, Sx_cap, d, es);
-        }
-        for (size_t li = 0; li < nl && !absorbed; ++li) {
-            if (M64) {          // the e1 tokens of the attached OCSR branch: rows [0, e1_M) of every image's key stream (as mg_generate)
-                GemmArgs ke = gemm_args(we.e1_pk, m->at<uint16_t>(m->dec[li].xkv), n * M64, 2 * inner, d);
-                set_heads(ke, H, M64, Sx_cap, w.xk + li * w.pool_stride + ent_off, HF_NATURAL, w.xv + li * w.pool_stride + ent_off, HF_NATURAL, nullptr, HF_NONE);
-                ke.heads.row_map = we.e1_map;
-                gemm(ke, EPI_HEADS, es);
-            }
-            GemmArgs kv = gemm_args(we.enc_pk, m->at<uint16_t>(m->dec[li].xkv), n * S_cap, 2 * inner, d);
-            set_heads(kv, H, S_cap, Sx_cap, w.xk + li * w.pool_stride + ent_off, HF_NATURAL, w.xv + li * w.pool_stride + ent_off, HF_NATURAL, nullptr, HF_NONE);
-            kv.heads.row_map = we.xrow;
-            if (m->st_row_tiles) { kv.row_tiles = we.row_tiles + 1; kv.n_row_tiles = we.row_tiles; }
-            gemm(kv, EPI_HEADS, es);
-        }
+        prepare_cross_kv(m, we, n, db, w.pool_stride, entry0, Sx_cap, M64, es);      // into the chunk's pool entries (as mg_generate)
         MG_LAUNCH(stream_chunk_done_kernel, dim3(1), dim3(64), 0, es, (const int*)we.xlen, w.xlen_pool, entry0, n, (const int*)we.counters, w.err);
         mg_event_record(e1, es);
         ++submitted;
@@ -1834,12 +1709,11 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
         if (announced == 0) { announce(true); }
         for (int g = 0; g < GROUP; ++g) {
             const bool timed_step = m->prof_every > 0 && (steps % m->prof_every) == 0;
-#ifndef MG_EMU
             if (graphed && !timed_step) {
-                if (hipGraphLaunch(m->stream_graph.exec, st) != hipSuccess) { quiesce(); return fail(MG_E_HIP, "%s: hipGraphLaunch failed", who); }
-            } else
-#endif
+                if (!m->stream_graph.launch(st)) { quiesce(); return fail(MG_E_HIP, "%s: hipGraphLaunch failed", who); }
+            } else {
                 decode_step(m, dc, 0, nullptr, timed_step, st);
+            }
             ++steps;
         }
         // counters back to the host, asynchronously; look at the oldest outstanding copy only when the ring is full
@@ -1864,15 +1738,8 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
     if (rc != MG_OK) return rc;
     for (int c = 0; c < (n_chunks < pool_chunks ? n_chunks : pool_chunks); ++c)
         m->stream_enc_ms += mg_event_elapsed_ms(m->chunk_ev[2 * c], m->chunk_ev[2 * c + 1]);     // the last pool_chunks chunks (statistics)
-    if (m->prof_used) {      // cross-attention brackets of the timed steps: keys streamed = live slots' pool entries at that step (approximated by the mean)
-        for (size_t i = 0; i + 2 < m->prof_used; i += 3) {
-            m->prof_ms += mg_event_elapsed_ms(m->prof_ev[i], m->prof_ev[i + 1]);
-            m->prof_empty_ms += mg_event_elapsed_ms(m->prof_ev[i + 1], m->prof_ev[i + 2]);
-            m->prof_n += 1;
-            m->prof_keys += (double)err2[1] / N * (N < slots ? N : slots);
-        }
-        m->prof_used = 0;
-    }
+    // keys streamed by a timed step = the live slots' pool entries at that step (approximated by the mean)
+    if (m->prof_used) accumulate_cross_profile(m, (double)err2[1] / N * (N < slots ? N : slots));
     m->stream_steps = steps;
     if (steps_host) *steps_host = steps;
     if (err_host != 0) return fail(MG_E_INPUT, "%s: %d token ids outside [0, vocab)", who, err_host);
@@ -1972,7 +1839,7 @@ int mg_set_decode_graph(mg_model* m, int enable) {
     if (!m) return fail(MG_E_ARG, "mg_set_decode_graph: null model");
     const int prev = m->use_graph;
     m->use_graph = enable < 0 ? 0 : (enable > 2 ? 1 : enable);
-    if (m->use_graph != 1) { m->step_graph.reset(); m->stream_graph.reset(); }      // (both captured steps: batch form and the greedy / beam queues)
+    if (m->use_graph != 1) { m->reset_step_graphs(); }      // (both captured steps: batch form and the greedy / beam queues)
     return prev;
 }
 int mg_decode_graph_active(const mg_model* m) { return m && m->graph_active ? 1 : 0; }
@@ -1982,7 +1849,7 @@ int mg_set_shared_gpu(mg_model* m, int shared) {
     const int prev = m->shared_gpu;
     m->shared_gpu = shared ? 1 : 0;
     if (m->shared_gpu) attention_step_allow_shared();
-    if (prev != m->shared_gpu) { m->step_graph.reset(); m->stream_graph.reset(); }      // (the captured launches carry the LDS request)
+    if (prev != m->shared_gpu) { m->reset_step_graphs(); }      // (the captured launches carry the LDS request)
     return prev;
 }
 int mg_set_cross_absorb(mg_model* m, int absorb, int key_splits) {
@@ -1995,7 +1862,7 @@ int mg_set_cross_absorb(mg_model* m, int absorb, int key_splits) {
     if (absorb && !xattn_supported(m->d, m->H)) return fail(MG_E_UNSUPPORTED, "mg_set_cross_absorb: d_model %d / %d heads have no absorbed form", m->d, m->H);
     m->absorb = absorb;
     if (key_splits) m->xa_split = key_splits;
-    m->step_graph.reset(); m->stream_graph.reset();      // (the captured steps hold the other form's launches and buffers)
+    m->reset_step_graphs();      // (the captured steps hold the other form's launches and buffers)
     return prev;
 }
 int mg_set_beam_cross_absorb(mg_model* m, int absorb, int key_splits) {
@@ -2008,7 +1875,7 @@ int mg_set_beam_cross_absorb(mg_model* m, int absorb, int key_splits) {
     if (absorb && !xattn_supported(m->d, m->H)) return fail(MG_E_UNSUPPORTED, "mg_set_beam_cross_absorb: d_model %d / %d heads have no absorbed form", m->d, m->H);
     m->beam_absorb = absorb;
     if (key_splits) m->xb_split = key_splits;
-    m->step_graph.reset(); m->stream_graph.reset();      // (the captured steps hold the other form's launches and buffers)
+    m->reset_step_graphs();      // (the captured steps hold the other form's launches and buffers)
     return prev;
 }
 // launches timed, their summed duration, and the summed number of (image, key) rows streamed per launch

@@ -6,6 +6,7 @@
 // the GEMM / attention kernels of the main path, the glue kernels are in k_ocr.hip.
 // Round-2 form: every operation its own launch, fp32 intermediates between GEMM and activation, eager decode steps.
 #include "mg_kernels.h"
+#include "mg_graph.h"
 #include "mg_ocr.h"
 #include "mg_swin.h"
 #include "../../include/mgrapher.h"
@@ -85,22 +86,19 @@ struct mg_ocr_model {
     // device step counter; replayed while the call's buffers and sizes match (MG_OCR_GRAPH=0: eager launches, same kernels)
     int use_graph = 1;
     bool graph_active = false;
-    struct Key { const void *ws, *out, *stream; int B, n_img, L, max_new; bool operator==(const Key& o) const { return ws == o.ws && out == o.out && stream == o.stream && B == o.B && n_img == o.n_img && L == o.L && max_new == o.max_new; } } gkey{};   // n_img: the text-side buffers are carved behind the vision buffers
-    bool gvalid = false;
-    struct SKey { const void *ws, *out, *out_len, *stream; int N, slots, L, max_new, chunk, n_img, ragged; bool operator==(const SKey& o) const { return ws == o.ws && out == o.out && out_len == o.out_len && stream == o.stream && N == o.N && slots == o.slots && L == o.L && max_new == o.max_new && chunk == o.chunk && n_img == o.n_img && ragged == o.ragged; } } skey{};   // chunk, n_img: the decode rows, K/V pages and slot table are carved behind the prefill region they size
-    bool svalid = false;
-#ifndef MG_EMU
-    hipGraphExec_t sexec = nullptr;
-    hipGraphExec_t gexec = nullptr;
-    hipStream_t own_stream = nullptr;
-    hipEvent_t fork_ev = nullptr;
-    void greset() { if (gexec) (void)hipGraphExecDestroy(gexec); gexec = nullptr; gvalid = false; }
-    void sreset() { if (sexec) (void)hipGraphExecDestroy(sexec); sexec = nullptr; svalid = false; }
-    ~mg_ocr_model() { greset(); sreset(); if (own_stream) (void)hipStreamDestroy(own_stream); if (fork_ev) (void)hipEventDestroy(fork_ev); }
-#else
-    void greset() { gvalid = false; }
-    void sreset() { svalid = false; }
-#endif
+    struct Key {       // batch form (n_img: the text-side buffers are carved behind the vision buffers)
+        const void *ws, *out, *stream;
+        int B, n_img, L, max_new;
+        MG_KEY_MEMBERS(Key, ws, out, stream, B, n_img, L, max_new)
+    };
+    struct SKey {      // queue form (chunk, n_img: the decode rows, K/V pages and slot table are carved behind the prefill region they size)
+        const void *ws, *out, *out_len, *stream;
+        int N, slots, L, max_new, chunk, n_img, ragged;
+        MG_KEY_MEMBERS(SKey, ws, out, out_len, stream, N, slots, L, max_new, chunk, n_img, ragged)
+    };
+    NullStreamFork fork;           // (destroyed in reverse order of declaration: the graphs before the stream they were captured on)
+    CapturedStep<Key> step_graph;
+    CapturedStep<SKey> stream_graph;
     template <typename T> T* at(size_t off) const { return (T*)(arena + off); }
     const float* rawp(const std::string& k) const { return (const float*)(arena + raw.at(k).off); }
 };
@@ -613,16 +611,8 @@ int mg_ocr_generate(mg_ocr_model* m, void* stream, void* ws, size_t ws_bytes, co
     carve(m, (char*)ws, B, n_img, L, max_new_tokens, false, &w);
     if (!ws || ws_bytes < w.total) return failf(MG_E_WORKSPACE, "mg_ocr_generate: workspace %zu < %zu bytes", ws_bytes, w.total);
     mgStream_t st = (mgStream_t)stream;
-#ifndef MG_EMU
-    // the legacy null stream cannot be captured: the call then runs on a stream the model owns, ordered after the caller's stream
-    // by an event and host-synchronised before returning (as mg_generate does)
-    if (m->use_graph == 1 && st == nullptr && !step_logits) {
-        if (!m->own_stream && hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking) != hipSuccess) m->own_stream = nullptr;
-        if (!m->fork_ev && hipEventCreateWithFlags(&m->fork_ev, hipEventDisableTiming) != hipSuccess) m->fork_ev = nullptr;
-        if (m->own_stream && m->fork_ev && hipEventRecord(m->fork_ev, st) == hipSuccess && hipStreamWaitEvent(m->own_stream, m->fork_ev, 0) == hipSuccess)
-            st = m->own_stream;
-    }
-#endif
+    // (a null stream cannot be captured; the call ends with a host synchronisation of the stream it ran on, as mg_generate does)
+    if (m->use_graph == 1 && !step_logits) st = m->fork.from(st);
     const mg_ocr_config& c = m->c;
     const int cap = round_up(L + max_new_tokens, 64), T_cap = round_up(L, 64);
     mg_memset_async(w.counters, 0, 16 * sizeof(int), st);
@@ -647,25 +637,13 @@ int mg_ocr_generate(mg_ocr_model* m, void* stream, void* ws, size_t ws_bytes, co
         greedy_select(g, st);
     };
     bool graphed = false;
-#ifndef MG_EMU
     if (m->use_graph == 1 && !step_logits && max_new_tokens > 1) {
         const mg_ocr_model::Key key{ws, out_ids, (const void*)st, B, n_img, L, max_new_tokens};
-        if (!(m->gvalid && m->gkey == key)) {
-            std::lock_guard<std::mutex> capture_lock(mg_capture_mutex());
-            m->greset();
-            hipGraph_t graph = nullptr;
-            if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                decode_step(m, w, B, L - 1, w.counters + 2, cap, st);   // position = L - 1 + step counter (>= 1 here)
-                select(0, w.counters + 2);
-                if (hipStreamEndCapture(st, &graph) == hipSuccess && graph &&
-                    hipGraphInstantiate(&m->gexec, graph, nullptr, nullptr, 0) == hipSuccess) { m->gkey = key; m->gvalid = true; }
-                if (graph) (void)hipGraphDestroy(graph);
-            }
-            (void)hipGetLastError();
-        }
-        graphed = m->gvalid;
+        graphed = m->step_graph.ensure(key, st, "mg_ocr_generate", [&] {
+            decode_step(m, w, B, L - 1, w.counters + 2, cap, st);   // position = L - 1 + step counter (>= 1 here)
+            select(0, w.counters + 2);
+        });
     }
-#endif
     m->graph_active = graphed;
     if (step_logits && capture_steps > 0)
         MG_LAUNCH(copy_f32_kernel, dim3(256), dim3(256), 0, st, (const float*)w.logits, step_logits, (size_t)B * c.vocab);
@@ -677,12 +655,9 @@ int mg_ocr_generate(mg_ocr_model* m, void* stream, void* ws, size_t ws_bytes, co
             mg_stream_sync(st);
             if (host_flag[0] == 0) break;
         }
-#ifndef MG_EMU
         if (graphed) {
-            if (hipGraphLaunch(m->gexec, st) != hipSuccess) return failf(MG_E_HIP, "mg_ocr_generate: hipGraphLaunch failed");
-        } else
-#endif
-        {
+            if (!m->step_graph.launch(st)) return failf(MG_E_HIP, "mg_ocr_generate: hipGraphLaunch failed");
+        } else {
             decode_step(m, w, B, L + t - 1, nullptr, cap, st);
             if (step_logits && t < capture_steps)
                 MG_LAUNCH(copy_f32_kernel, dim3(256), dim3(256), 0, st, (const float*)w.logits, step_logits + (size_t)t * B * c.vocab, (size_t)B * c.vocab);
@@ -743,14 +718,7 @@ int mg_ocr_generate_stream_ragged(mg_ocr_model* m, void* stream, void* ws, size_
     mg_ocr_stream_workspace_bytes(m, N, n_img, L, max_new_tokens, slots, chunk, &need);
     if (!ws || ws_bytes < need) return failf(MG_E_WORKSPACE, "mg_ocr_generate_stream: workspace %zu < %zu bytes", ws_bytes, need);
     mgStream_t st = (mgStream_t)stream;
-#ifndef MG_EMU
-    if (m->use_graph == 1 && st == nullptr) {
-        if (!m->own_stream && hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking) != hipSuccess) m->own_stream = nullptr;
-        if (!m->fork_ev && hipEventCreateWithFlags(&m->fork_ev, hipEventDisableTiming) != hipSuccess) m->fork_ev = nullptr;
-        if (m->own_stream && m->fork_ev && hipEventRecord(m->fork_ev, st) == hipSuccess && hipStreamWaitEvent(m->own_stream, m->fork_ev, 0) == hipSuccess)
-            st = m->own_stream;
-    }
-#endif
+    if (m->use_graph == 1) st = m->fork.from(st);
     const mg_ocr_config& c = m->c;
     const int cap = round_up(L + max_new_tokens, 64), T_cap = round_up(L, 64);
     // workspace: [prefill chunk | decode rows | K pages | V pages | first tokens | slot table]
@@ -832,36 +800,18 @@ int mg_ocr_generate_stream_ragged(mg_ocr_model* m, void* stream, void* ws, size_
     };
     slot_refill(tab, w.next_ids, w.unfinished, slots, st);          // the first pages take their slots
     bool graphed = false;
-#ifndef MG_EMU
     if (m->use_graph == 1) {
         const mg_ocr_model::SKey key{ws, out_ids, out_len, (const void*)st, N, slots, L, max_new_tokens, chunk, n_img, prompt_len ? 1 : 0};
-        if (!(m->svalid && m->skey == key)) {
-            std::lock_guard<std::mutex> capture_lock(mg_capture_mutex());
-            m->sreset();
-            hipGraph_t graph = nullptr;
-            if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                step();
-                if (hipStreamEndCapture(st, &graph) == hipSuccess && graph && hipGraphInstantiate(&m->sexec, graph, nullptr, nullptr, 0) == hipSuccess) {
-                    m->skey = key; m->svalid = true;
-                }
-                if (graph) (void)hipGraphDestroy(graph);
-            }
-            (void)hipGetLastError();
-        }
-        graphed = m->svalid;
+        graphed = m->stream_graph.ensure(key, st, "mg_ocr_generate_stream", step);
     }
-#endif
     m->graph_active = graphed;
     long steps = 0;
     int host[16] = {0};
     const long limit = (long)N * max_new_tokens / 1 + 64;
     while (host[1] < N) {
         for (int g8 = 0; g8 < 8; ++g8) {
-#ifndef MG_EMU
-            if (graphed) { if (hipGraphLaunch(m->sexec, st) != hipSuccess) return failf(MG_E_HIP, "mg_ocr_generate_stream: hipGraphLaunch failed"); }
-            else
-#endif
-                step();
+            if (graphed) { if (!m->stream_graph.launch(st)) return failf(MG_E_HIP, "mg_ocr_generate_stream: hipGraphLaunch failed"); }
+            else step();
             ++steps;
         }
         mg_memcpy_async(host, sctr, sizeof host, st);
