@@ -168,8 +168,9 @@ int mg_generate_scored(mg_model* m, void* stream, void* ws, size_t ws_bytes, con
  * Runs under the decode
  * graph like the other batch forms (every option is part of the captured step's key); mg_debug_decode_capture's logits capture works, its
  * forced ids do not (MG_E_UNSUPPORTED).  Vocabulary <= 36 864 (the selection keeps the row in registers).
- * NOT built: the queue forms (mg_generate_stream*) and the OCR stage under sampling, one cross-attention pass shared by the samples of an
- * image (the beam form's group = num_return), a Gumbel-max variant on the fused lm_head tail, beam-sample. */
+ * The greedy queue has a sampled form, mg_generate_stream_sampled (below, after mg_generate_stream).
+ * NOT built: the beam and OCR queues and the OCR stage under sampling, one cross-attention pass shared by the samples of an image (the
+ * beam form's group = num_return), a Gumbel-max variant on the fused lm_head tail, beam-sample. */
 typedef struct mg_sample_opts {
     float temperature;
     int top_k;
@@ -198,6 +199,22 @@ int mg_stream_workspace_bytes(const mg_model* m, int chunk, int L, int slots, in
 int mg_generate_stream(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
                        const uint8_t* attention_mask, const float* pixel_values, int N, int L, int chunk, int slots, int pool_chunks,
                        int max_length, int min_length, int64_t* out_ids, int32_t* out_len, long* steps_host);
+/* The same queue under SAMPLING (mg_sample_opts, see mg_generate_sampled): a queue of N images with num_return samples each is a queue of
+ * N * num_return SEQUENCES, sequence n * num_return + j = sample j of image n.  `slots` (<= 256, <= pool_chunks * chunk * num_return)
+ * greedy-form decode rows work through the sequences in order; the samples of an image may sit in different slots at different times and
+ * end independently.  One encoder pass and one pool entry per image whatever num_return is: an entry is reused only when every sample of
+ * its image has finished.  The draw of sequence q at a column uses the Philox counter (stream_ids ? stream_ids[q] : q, column) - the
+ * sequence's place in the queue, never its slot - so with the cross-attention form pinned its ids, length and token scores are exactly
+ * those of mg_generate_sampled on its image alone with that stream id, and do not depend on chunk / slots / pool_chunks.
+ *   outputs  out_ids [N * num_return][max_length], out_len [N * num_return], opts->token_scores [N * num_return][max_length - 1] (nullable),
+ *            opts->stream_ids [N * num_return] (nullable: the sequence index)
+ * WORKSPACE: mg_stream_workspace_bytes(chunk, L, slots, pool_chunks) - the rows are greedy-form rows; the cross-attention form follows
+ * mg_set_cross_absorb by `slots`, as for the greedy queue.  Checks: temperature > 0, top_k >= 0, 0 < top_p <= 1, num_return >= 1 (MG_E_ARG),
+ * vocabulary <= 36 864 (MG_E_UNSUPPORTED).  Every option is part of the captured step's key.  SYNCHRONISES before returning. */
+int mg_generate_stream_sampled(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
+                               const uint8_t* attention_mask, const float* pixel_values, int N, int L, int chunk, int slots,
+                               int pool_chunks, int max_length, int min_length, int64_t* out_ids, int32_t* out_len, long* steps_host,
+                               const mg_sample_opts* opts);
 /* The same queue with BEAM SEARCH - the reference's shipped decode mode (/root/reference/config/predict.yaml:12-13 beam_search: True;
  * utils_evaluation.py:269-285 generate(num_beams=5, max_length=512)): `slots` IMAGE slots of num_beams rows each (slots * num_beams <= 256)
  * work through the queue; an image whose own stopping condition holds (stock 5.15 generation/utils.py:3055-3075 for that image alone - in a

@@ -66,7 +66,7 @@ struct BatchStepKey {        // mg_generate / mg_generate_sampled
     MG_KEY_MEMBERS(BatchStepKey, ws, out_ids, step_top2, stream, B, L, K, max_length, min_length, early_stopping, M_e1, length_penalty,
                    token_scores, num_return, top_k, temperature, top_p, seed, stream_ids)
 };
-struct QueueStepKey {        // mg_generate_stream*: greedy and beam queues
+struct QueueStepKey {        // mg_generate_stream*: greedy, sampled and beam queues
     const void *ws, *out_ids, *out_len, *stream;
     int N, L, chunk, slots, pool_chunks, num_beams, max_length, min_length;
     bool early_stopping;
@@ -75,8 +75,15 @@ struct QueueStepKey {        // mg_generate_stream*: greedy and beam queues
     // token-score pointer
     const void *out_scores, *token_scores, *beam_indices;
     int num_return;
+    // sampled queue (mg_generate_stream_sampled): the selection and the refill launches hold every one of these (num_return = samples per
+    // image there; not a sampled call: all 0, so a greedy call never replays a sampled step)
+    int top_k;
+    float temperature, top_p;
+    uint64_t seed;
+    const void* stream_ids;
     MG_KEY_MEMBERS(QueueStepKey, ws, out_ids, out_len, stream, N, L, chunk, slots, pool_chunks, num_beams, max_length, min_length,
-                   early_stopping, length_penalty, out_scores, token_scores, beam_indices, num_return)
+                   early_stopping, length_penalty, out_scores, token_scores, beam_indices, num_return, top_k, temperature, top_p, seed,
+                   stream_ids)
 };
 
 struct mg_model {
@@ -450,6 +457,7 @@ void carve(const mg_model* m, char* base, int B, int L, int K, int max_len, int 
 // stream counters (device, `ctr`): [0] live slots after the last step, [1] images finished, [2] steps run, [3] unused,
 // [4] queue head (next image to hand to a slot), [5] images whose cross K/V are in the pool, [7] oldest live image
 // (every image below it has finished: its pool entry may be overwritten), [8] N
+// sampled queue (SlotTable::nsamp sequences per image): [1], [4], [7], [8] count SEQUENCES, [5] stays in images
 struct StreamWs {
     Ws enc;                   // encoder workspace of one chunk
     DecodeBufs dec;           // decode rows; cross K/V as a pool [layer][pool entry][H][Sx_cap][64] (absorbed form: pool of encoder states [pool entry][Sx_cap][d])
@@ -640,7 +648,7 @@ struct DecodeCtx : DecodeBufs {
     // scored calls: greedy token log-probabilities [rows or images][max_length - 1] (nullable); beam queue: the n-best output
     float* token_scores;
     BeamOut nbest;
-    const mg_sample_opts* samp;   // sampled call (mg_generate_sampled): the selection is sample_select; rows of an image read its K/V through slots.pool
+    const mg_sample_opts* samp;   // sampled call (mg_generate_sampled, mg_generate_stream_sampled): the selection is sample_select; rows of an image read its K/V through slots.pool
 };
 
 // Decode step, 6 launches per layer: QKV -> self-attention -> [O residual | cross-Q] -> cross-attention ->
@@ -783,7 +791,8 @@ static void decode_step(mg_model* m, const DecodeCtx& c, int t, const int* tdev,
             sa.temperature = c.samp->temperature; sa.top_k = c.samp->top_k; sa.top_p = c.samp->top_p; sa.seed = c.samp->seed;
             sa.stream_ids = c.samp->stream_ids; sa.next_ids = c.next_ids; sa.out_ids = out_ids; sa.max_len = max_length;
             sa.pos = g.pos; sa.pos_dev = tdev; sa.unfinished = c.unfinished; sa.n_unfinished = g.n_unfinished; sa.top2 = g.top2;
-            sa.step_ctr = counters; sa.token_scores = c.token_scores; sa.ts_ld = max_length - 1;
+            sa.step_ctr = g.step_ctr; sa.token_scores = c.token_scores; sa.ts_ld = max_length - 1;
+            sa.slots = c.slots;            // queue form: the row's column, output row and random stream come from the slot table
             sample_select(sa, st);
         } else if (fused_tail) {
             g.ptop = c.ptop; g.stopv = c.stopv; g.ntiles = ldl / 32;
@@ -1582,7 +1591,8 @@ int mg_stream_encoder_mode(mg_model* m, int mode, const uint32_t* cu_mask, int n
 static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
                                 const uint8_t* attention_mask, const float* pixel_values, int N, int L, int chunk, int slots, int pool_chunks,
                                 int K, int max_length, int min_length, float length_penalty, int early_stopping, int64_t* out_ids,
-                                int32_t* out_len, float* out_scores, long* steps_host, const char* who, const mg_gen_opts* opts) {
+                                int32_t* out_len, float* out_scores, long* steps_host, const char* who, const mg_gen_opts* opts,
+                                const mg_sample_opts* samp = nullptr) {
     entry_drain();
     if (!m || !ws || !input_ids || !bbox || !pixel_values || !out_ids || !out_len) return fail(MG_E_ARG, "%s: null argument", who);
     MG_ONE_CALL(m, "mg_generate_stream");
@@ -1590,12 +1600,24 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
     if (N < 1 || L < 1 || chunk < 1 || pool_chunks < 2) return fail(MG_E_SHAPE, "%s: N, L, chunk must be >= 1, pool_chunks >= 2", who);
     if (K < 1 || K > 8) return fail(MG_E_UNSUPPORTED, "%s: num_beams must be in [1, 8]", who);
     if (slots < 1 || (long)slots * K > 256) return fail(MG_E_UNSUPPORTED, "%s: slots * num_beams must be in [1, 256]", who);
-    if (slots > pool_chunks * chunk) return fail(MG_E_SHAPE, "%s: slots (%d) exceed the %d pool entries", who, slots, pool_chunks * chunk);
+    // sampled queue: N images x S samples = NQ sequences; `slots` rows decode sequences, the pool holds images
+    if (samp) {
+        if (!(samp->temperature > 0.f)) return fail(MG_E_ARG, "%s: temperature must be > 0", who);
+        if (samp->top_k < 0) return fail(MG_E_ARG, "%s: top_k must be >= 0 (0 = off)", who);
+        if (!(samp->top_p > 0.f) || samp->top_p > 1.f) return fail(MG_E_ARG, "%s: top_p must be in (0, 1] (1 = off)", who);
+        if (samp->num_return < 1) return fail(MG_E_ARG, "%s: num_return must be >= 1", who);
+        if ((long)N * samp->num_return > 0x7fffffffL) return fail(MG_E_SHAPE, "%s: N * num_return exceeds 2^31 - 1 sequences", who);
+        if (!sample_select_supported(m->V)) return fail(MG_E_UNSUPPORTED, "%s: vocabulary of %d exceeds the selection kernel's 36864", who, m->V);
+    }
+    const int S = samp ? samp->num_return : 1;
+    const long NQ = (long)N * S;
+    if ((long)slots > (long)pool_chunks * chunk * S)
+        return fail(MG_E_SHAPE, "%s: slots (%d) exceed the %d pool entries%s", who, slots, pool_chunks * chunk, S > 1 ? " x num_return" : "");
     if (max_length < 2 || max_length > m->T_cap) return fail(MG_E_SHAPE, "%s: max_length must be in [2, %d]", who, m->T_cap);
     if (m->dbg_logits || m->dbg_forced) return fail(MG_E_STATE, "%s: the decode-capture instrumentation is for mg_generate", who);
     const int num_return = opts ? opts->num_return : 1;
     if (num_return < 1 || num_return > K) return fail(MG_E_ARG, "%s: num_return (%d) must be in [1, num_beams = %d]", who, num_return, K);
-    float* token_scores = opts ? opts->token_scores : nullptr;
+    float* token_scores = samp ? samp->token_scores : (opts ? opts->token_scores : nullptr);
     if (opts && K > 1) out_scores = opts->seq_scores;
     const int R = slots * K;                         // decode rows
     StreamWs w;
@@ -1623,7 +1645,7 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
     // slot table, outputs
     const int64_t start = m->c.decoder_start_token_id, pad = m->c.pad_token_id;
     const DecodeBufs& db = w.dec;
-    MG_LAUNCH(stream_init_kernel, dim3(64), dim3(256), 0, st, out_ids, out_len, N, max_length, start, pad, db.unfinished, w.pos, w.img, w.pool,
+    MG_LAUNCH(stream_init_kernel, dim3(64), dim3(256), 0, st, out_ids, out_len, (int)NQ, max_length, start, pad, db.unfinished, w.pos, w.img, w.pool,
               db.next_ids, R, w.ctr, w.err);
     mg_memset_async(w.bpool, 0, (size_t)round_up(slots, 32) * sizeof(int), st);
     mg_memset_async(w.assign, 0xFF, (size_t)round_up(slots, 32) * sizeof(int), st);
@@ -1645,10 +1667,12 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
     dc.bpool = w.bpool; dc.assign = w.assign; dc.out_len = out_len; dc.out_scores = out_scores;
     if (K == 1 && token_scores) {      // columns an image does not reach (after its EOS) hold 0
         dc.token_scores = token_scores;
-        mg_memset_async(token_scores, 0, (size_t)N * (max_length - 1) * sizeof(float), st);
+        mg_memset_async(token_scores, 0, (size_t)NQ * (max_length - 1) * sizeof(float), st);
     }
+    dc.samp = samp;
     dc.nbest = BeamOut{num_return, opts ? opts->beam_indices : nullptr, K > 1 ? token_scores : nullptr};
     dc.slots = SlotTable{w.pos, w.img, w.pool, w.ctr, out_len, entries, (int)start};
+    dc.slots.nsamp = S;
     // the step as a graph (every step-dependent value lives in the slot table)
     bool graphed = false;
     if (m->use_graph == 1) {
@@ -1657,6 +1681,10 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
         key.N = N; key.L = L; key.chunk = chunk; key.slots = slots; key.pool_chunks = pool_chunks; key.num_beams = K;
         key.max_length = max_length; key.min_length = min_length; key.early_stopping = early_stopping != 0; key.length_penalty = length_penalty;
         key.out_scores = out_scores; key.token_scores = token_scores; key.beam_indices = dc.nbest.beam_indices; key.num_return = num_return;
+        if (samp) {
+            key.num_return = S; key.top_k = samp->top_k; key.temperature = samp->temperature; key.top_p = samp->top_p; key.seed = samp->seed;
+            key.stream_ids = samp->stream_ids;
+        }
         graphed = m->stream_graph.ensure(key, st, who, [&] { decode_step(m, dc, 0, nullptr, false, st); });
     }
     m->graph_active = graphed;
@@ -1695,17 +1723,19 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
     int rc = MG_OK;
     // error returns from the loop: nothing enqueued by this call may still be writing ws / out_ids / out_len when it returns
     auto quiesce = [&]() { if (es != st) mg_stream_sync(es); mg_stream_sync(st); };
-    while (done_host < N) {
+    // head / done / oldest come back in sequences (sampled queue: S per image); chunks, the pool and `announced` are in images
+    while (done_host < NQ) {
         // feed the encoder stream: chunk c overwrites the pool entries of chunk c - pool_chunks, whose images must all have
         // finished (oldest live image known to the host, a few steps late: conservative)
-        while (submitted < n_chunks && (submitted < pool_chunks || oldest_host >= (submitted - pool_chunks + 1) * chunk) &&
+        // (an entry is overwritten only when every sample of its image has finished: the oldest live sequence's image)
+        while (submitted < n_chunks && (submitted < pool_chunks || oldest_host / S >= (submitted - pool_chunks + 1) * chunk) &&
                (es != st || submitted == announced)) {
             if ((rc = submit_chunk()) != MG_OK) { quiesce(); return rc; }
             if (es == st) break;              // serial mode: one chunk, then decode until the slots run dry
         }
         // hand finished chunks to the slots; when no slot is live and the queue is empty the decode stream has to wait for one
-        const bool starving = live_host == 0 && head_host >= announced * chunk;     // (late view; still true now: nothing was announced since)
-        while (announced < submitted && announce(starving && announced * chunk <= head_host)) {}
+        const bool starving = live_host == 0 && head_host >= (long)announced * chunk * S;     // (late view; still true now: nothing was announced since)
+        while (announced < submitted && announce(starving && (long)announced * chunk * S <= head_host)) {}
         if (announced == 0) { announce(true); }
         for (int g = 0; g < GROUP; ++g) {
             const bool timed_step = m->prof_every > 0 && (steps % m->prof_every) == 0;
@@ -1727,7 +1757,7 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
             live_host = h[0]; done_host = h[1]; head_host = h[4]; oldest_host = h[7];
             ++rb_seen;
         }
-        if (steps > (long)N * max_length + 64L * n_chunks + 1024) { quiesce(); return fail(MG_E_HIP, "%s: no progress (%d of %d images after %ld steps)", who, done_host, N, steps); }
+        if (steps > NQ * max_length + 64L * n_chunks + 1024) { quiesce(); return fail(MG_E_HIP, "%s: no progress (%d of %ld sequences after %ld steps)", who, done_host, NQ, steps); }
     }
     int err2[2] = {0, 0};
     int& err_host = err2[0];
@@ -1739,7 +1769,7 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
     for (int c = 0; c < (n_chunks < pool_chunks ? n_chunks : pool_chunks); ++c)
         m->stream_enc_ms += mg_event_elapsed_ms(m->chunk_ev[2 * c], m->chunk_ev[2 * c + 1]);     // the last pool_chunks chunks (statistics)
     // keys streamed by a timed step = the live slots' pool entries at that step (approximated by the mean)
-    if (m->prof_used) accumulate_cross_profile(m, (double)err2[1] / N * (N < slots ? N : slots));
+    if (m->prof_used) accumulate_cross_profile(m, (double)err2[1] / N * (NQ < slots ? NQ : slots));
     m->stream_steps = steps;
     if (steps_host) *steps_host = steps;
     if (err_host != 0) return fail(MG_E_INPUT, "%s: %d token ids outside [0, vocab)", who, err_host);
@@ -1759,6 +1789,18 @@ int mg_generate_stream_scored(mg_model* m, void* stream, void* ws, size_t ws_byt
                               int max_length, int min_length, int64_t* out_ids, int32_t* out_len, long* steps_host, const mg_gen_opts* opts) {
     return generate_stream_impl(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, N, L, chunk, slots, pool_chunks, 1,
                                 max_length, min_length, 1.0f, 0, out_ids, out_len, nullptr, steps_host, "mg_generate_stream", opts);
+}
+// The greedy queue under sampling: a queue of N * opts->num_return sequences (sequence n * num_return + j = sample j of image n) on `slots`
+// greedy-form rows; one encoder pass and one pool entry per image.  Sequence q's ids equal those of a one-image mg_generate_sampled call
+// on its image with stream id q (or stream_ids[q]): tests/test_sampling_stream.py.
+int mg_generate_stream_sampled(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
+                               const uint8_t* attention_mask, const float* pixel_values, int N, int L, int chunk, int slots,
+                               int pool_chunks, int max_length, int min_length, int64_t* out_ids, int32_t* out_len, long* steps_host,
+                               const mg_sample_opts* opts) {
+    if (!opts) return fail(MG_E_ARG, "mg_generate_stream_sampled: null options");
+    return generate_stream_impl(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, N, L, chunk, slots, pool_chunks, 1,
+                                max_length, min_length, 1.0f, 0, out_ids, out_len, nullptr, steps_host, "mg_generate_stream_sampled", nullptr,
+                                opts);
 }
 int mg_stream_beam_workspace_bytes(const mg_model* m, int chunk, int L, int slots, int pool_chunks, int num_beams, int max_length, size_t* out_bytes) {
     if (!m || !out_bytes || chunk < 1 || L < 1 || slots < 1 || pool_chunks < 2 || num_beams < 1 || num_beams > 8 || max_length < 2)

@@ -509,7 +509,8 @@ __global__ __launch_bounds__(64) void slot_refill_kernel(SlotTable s, int64_t* n
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     int* c = s.ctr;
     int head = c[4], done_add = 0;
-    const int ready = c[5];
+    const int S = s.nsamp;                  // sequences per image: head / img / done count sequences, ready and the pool images
+    const int ready = c[5] * S;
     int n_live = 0, oldest = 0x7fffffff;
     for (int r = 0; r < rows; ++r) {
         int unf = s_unf[r], img = s_img[r];
@@ -525,7 +526,7 @@ __global__ __launch_bounds__(64) void slot_refill_kernel(SlotTable s, int64_t* n
                 if (stop) { s.out_len[i] = 1; ++done_add; continue; }
             }
             s.img[r] = i;
-            s.pool[r] = i % s.pool_cap;
+            s.pool[r] = (i / S) % s.pool_cap;
             s.pos[r] = 0;
             next_ids[r] = tok;
             unfinished[r] = 1;
@@ -536,7 +537,7 @@ __global__ __launch_bounds__(64) void slot_refill_kernel(SlotTable s, int64_t* n
     c[4] = head;
     if (done_add) c[1] += done_add;
     c[0] = n_live;
-    c[7] = n_live ? oldest : head;      // every image below this index has finished
+    c[7] = n_live ? oldest : head;      // every sequence below this index has finished
     c[2] += 1;
 }
 void slot_refill(const SlotTable& s, int64_t* next_ids, int* unfinished, int rows, mgStream_t stream) {

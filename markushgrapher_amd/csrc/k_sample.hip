@@ -109,7 +109,9 @@ MG_DEV uint32_t ss_radix_select(const uint32_t (&keys)[NQ * 4], const uint32_t (
     return prefix;
 }
 
-template <int NQ, int NT>
+// QUEUE: the continuous decoder's form (SampleArgs::slots, mg_kernels.h) - the row's column, output row and random stream are those of
+// the sequence in the slot (three wave-uniform scalars); everything that decides the token is the batch form's code.
+template <int NQ, int NT, bool QUEUE>
 __global__ __launch_bounds__(NT) void sample_select_kernel(SampleArgs a) {
     MG_DYN_SMEM(smem);
     u64* hist = (u64*)smem;                  // [256][SS_COPIES]
@@ -118,8 +120,12 @@ __global__ __launch_bounds__(NT) void sample_select_kernel(SampleArgs a) {
     float* rv = (float*)(sel + 2);           // [16][2]
     int* ri = (int*)(rv + 32);               // [16]
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int pos = a.pos_dev ? *a.pos_dev + a.pos : a.pos;      // column written
-    const int unf = a.unfinished[row];
+    const int unf = a.unfinished[row];       // (queue form: 0 = idle slot, computed on stale inputs - nothing is written, nothing is drawn)
+    // Queue form: both slot-table loads stay HERE, in front of the first barrier.  The lane that holds the draw later stores slots.pos[row]
+    // and clears slots.img[row] while other waves may still be computing the target from them (their first use, the Philox call, comes
+    // after the last barrier): a load moved down towards that use would race with those stores.
+    const int pos = QUEUE ? a.slots.pos[row] + 1 : (a.pos_dev ? *a.pos_dev + a.pos : a.pos);      // column written
+    const int seq = QUEUE ? a.slots.img[row] : row;              // row of out_ids / token_scores / stream_ids
     int64_t tok = (int64_t)a.pad;
     float score = 0.f, b1 = 0.f, b2 = 0.f;
     bool writer = tid == 0;                  // the thread that does the row's bookkeeping: thread 0 of a finished row, else the one that holds the draw
@@ -202,7 +208,7 @@ __global__ __launch_bounds__(NT) void sample_select_kernel(SampleArgs a) {
         u64 total = 0, before = 0;
         for (int ww = 0; ww < NT / 64; ++ww) { if (ww == w) before = total; total += wtot[ww]; }
         uint32_t rnd[4];
-        philox4x32_10(a.seed, a.stream_ids ? a.stream_ids[row] : (uint64_t)row, (uint32_t)pos, rnd);
+        philox4x32_10(a.seed, a.stream_ids ? a.stream_ids[seq] : (uint64_t)seq, (uint32_t)pos, rnd);
         const u64 r = ((u64)rnd[1] << 32) | rnd[0];
         const u64 target = __umul64hi(r, total);             // in [0, total)
         writer = false;
@@ -246,6 +252,21 @@ __global__ __launch_bounds__(NT) void sample_select_kernel(SampleArgs a) {
         }
     }
     if (writer) {
+        if (QUEUE) {
+            // greedy_select_kernel's stream branch, store for store: a row that ends frees its slot (slot_refill hands it the next sequence)
+            if (!unf) return;
+            a.next_ids[row] = tok;
+            a.slots.pos[row] = pos;
+            if (pos < a.max_len) a.out_ids[(size_t)seq * a.max_len + pos] = tok;
+            if (a.token_scores && pos < a.max_len) a.token_scores[(size_t)seq * a.ts_ld + pos - 1] = score;
+            if (tok == (int64_t)a.eos || pos + 1 >= a.max_len) {
+                a.unfinished[row] = 0;
+                a.slots.img[row] = -1;
+                a.slots.out_len[seq] = pos + 1 < a.max_len ? pos + 1 : a.max_len;
+                atomicAdd(a.slots.ctr + 1, 1);
+            }
+            return;
+        }
         a.next_ids[row] = tok;
         if (pos < a.max_len) a.out_ids[(size_t)row * a.max_len + pos] = tok;
         if (a.token_scores && pos < a.max_len) a.token_scores[(size_t)row * a.ts_ld + pos - 1] = unf ? score : 0.f;
@@ -276,9 +297,15 @@ bool sample_select_supported(int V) { return V >= 1 && V <= 4096 * 9; }
 
 void sample_select(const SampleArgs& a, mgStream_t stream) {
     const size_t lds = (256 * SS_COPIES + 16 + 2) * sizeof(u64) + 32 * sizeof(float) + 16 * sizeof(int);
-    if (a.V <= 4096) MG_LAUNCH((sample_select_kernel<1, 1024>), dim3(a.rows), dim3(1024), lds, stream, a);
-    else if (a.V <= 4096 * 3) MG_LAUNCH((sample_select_kernel<3, 1024>), dim3(a.rows), dim3(1024), lds, stream, a);
-    else MG_LAUNCH((sample_select_kernel<18, 512>), dim3(a.rows), dim3(512), lds, stream, a);
+    if (a.slots.pos) {
+        if (a.V <= 4096) MG_LAUNCH((sample_select_kernel<1, 1024, true>), dim3(a.rows), dim3(1024), lds, stream, a);
+        else if (a.V <= 4096 * 3) MG_LAUNCH((sample_select_kernel<3, 1024, true>), dim3(a.rows), dim3(1024), lds, stream, a);
+        else MG_LAUNCH((sample_select_kernel<18, 512, true>), dim3(a.rows), dim3(512), lds, stream, a);
+        return;
+    }
+    if (a.V <= 4096) MG_LAUNCH((sample_select_kernel<1, 1024, false>), dim3(a.rows), dim3(1024), lds, stream, a);
+    else if (a.V <= 4096 * 3) MG_LAUNCH((sample_select_kernel<3, 1024, false>), dim3(a.rows), dim3(1024), lds, stream, a);
+    else MG_LAUNCH((sample_select_kernel<18, 512, false>), dim3(a.rows), dim3(512), lds, stream, a);
 }
 
 }  // namespace mg

@@ -371,18 +371,21 @@ void embed_rows(const int64_t* ids, const uint16_t* tok_emb, float* h, int rows,
 
 // Slot table of the continuous decoder (mg_generate_stream, engine.hip): `slots` decode rows work through a queue of images; a
 // row that ends (EOS or max_length) frees its slot, the refill kernel hands it the next image whose cross K/V is in the pool.
+// Sampled queue (mg_generate_stream_sampled): the queue holds SEQUENCES, nsamp per image - sequence q = n * nsamp + j is sample j of
+// image n.  img / out_len / the head and done counters are in sequences, the ready counter and the pool stay in images.
 struct SlotTable {
     int* pos;          // [slots] position of the token fed to this step (0 = the start token); null = batch mode (no slot table)
-    int* img;          // [slots] image decoded in the slot (row of out_ids), -1 = idle
-    int* pool;         // [slots] cross K/V pool entry of that image
+    int* img;          // [slots] sequence decoded in the slot (row of out_ids), -1 = idle
+    int* pool;         // [slots] cross K/V pool entry of that sequence's image
     int* ctr;          // stream counters (layout: engine.hip)
-    int* out_len;      // [N] valid columns of every finished image
+    int* out_len;      // [N * nsamp] valid columns of every finished sequence
     int pool_cap;      // entries of the K/V pool (image i lives in entry i % pool_cap)
     int start_id;
     // ChemicalOCR queue form: a sequence enters a slot with the token its PREFILL selected (column 0 already written) instead of a
     // start token; one that began with a stop token (or max_len 1) is finished before it ever takes a slot
     const int64_t* first_tok;   // [N], null = start_id
     int n_stop, stop[4], max_len;
+    int nsamp = 1;     // sequences per image (greedy, beam and OCR queues: 1)
 };
 struct ArgmaxArgs {
     const float* logits;     // [rows][ldl]
@@ -425,7 +428,10 @@ struct ArgmaxArgs {
 void greedy_select(const ArgmaxArgs& a, mgStream_t stream);
 void greedy_select_fused(const ArgmaxArgs& a, mgStream_t stream);
 // Sampled selection (k_sample.hip; stock generation/utils.py::_sample with do_sample = True): MinLength, temperature, top-k, top-p in
-// stock's order, then one draw per live row.  Batch form only; bookkeeping (unfinished, n_unfinished, step_ctr, pos_dev, top2) as ArgmaxArgs.
+// stock's order, then one draw per live row.  Batch form: bookkeeping (unfinished, n_unfinished, step_ctr, pos_dev, top2) as ArgmaxArgs.
+// Queue form (slots.pos non-null; the `stream` branch of greedy_select_kernel): a row writes its own column slots.pos[row] + 1 of sequence
+// q = slots.img[row] (out_ids[q], token_scores[q]), draws at counter (stream_ids ? stream_ids[q] : q, that column) - the sequence's
+// place in the queue, never the slot - and frees its slot when it ends; idle slots write and draw nothing; no step_ctr, no top2.
 struct SampleArgs {
     const float* logits;     // [rows][ldl]
     int rows, V, ldl;
@@ -435,6 +441,7 @@ struct SampleArgs {
     float top_p;             // >= 1 = off; ties at the boundary value are all kept
     uint64_t seed;           // Philox4x32-10 key
     const uint64_t* stream_ids;   // [rows] counter words 0 / 1 of a row's stream (null: the row index); word 2 = the column written
+                                  // (queue form: [sequences of the queue], null: the sequence index)
     int64_t* next_ids;
     int64_t* out_ids;        // [rows][max_len]
     int max_len, pos;
@@ -445,6 +452,7 @@ struct SampleArgs {
     int* step_ctr;
     float* token_scores;     // nullable, [rows][ts_ld]: log-probability of the drawn token under the warped distribution, column pos - 1
     int ts_ld;
+    SlotTable slots;         // continuous decoding (slots.pos == null: batch form)
 };
 bool sample_select_supported(int V);     // the row is held in registers: V <= 36 864
 void sample_select(const SampleArgs& a, mgStream_t stream);

@@ -34,7 +34,7 @@ class MgGenOpts(C.Structure):
 
 
 class MgSampleOpts(C.Structure):
-    """include/mgrapher.h mg_sample_opts: the options of mg_generate_sampled."""
+    """include/mgrapher.h mg_sample_opts: the options of mg_generate_sampled and mg_generate_stream_sampled."""
     _fields_ = [("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float), ("seed", C.c_uint64), ("stream_ids", C.c_void_p),
                 ("num_return", C.c_int), ("token_scores", C.c_void_p)]
 
@@ -158,6 +158,7 @@ class Engine:
         L.mg_generate_stream_beam.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + \
                                              [C.c_int] * 8 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_long)]
         L.mg_generate_stream_scored.argtypes = L.mg_generate_stream.argtypes + [C.POINTER(MgGenOpts)]
+        L.mg_generate_stream_sampled.argtypes = L.mg_generate_stream.argtypes + [C.POINTER(MgSampleOpts)]
         L.mg_generate_stream_beam_scored.argtypes = L.mg_generate_stream_beam.argtypes[:-3] + [C.c_void_p, C.POINTER(C.c_long),
                                                                                                C.POINTER(MgGenOpts)]
         L.mg_stream_encoder_mode.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -495,6 +496,55 @@ class Engine:
         opts, ts, _, _ = self._scored_out("stream", N, max_length, False)
         self._chk(self.lib.mg_generate_stream_scored(*args, C.byref(opts)))
         return self.mem.copy(out[0]), self.mem.copy(out[1]), int(steps.value), self.mem.copy(ts)
+
+    def generate_stream_sampled(self, input_ids, bbox, attention_mask, pixel_values, max_length=512, min_length=0, temperature=1.0, top_k=0,
+                                top_p=1.0, seed=0, num_return=1, stream_ids=None, chunk=32, slots=32, pool_chunks=3, return_scores=False):
+        """The greedy queue under sampling (include/mgrapher.h mg_generate_stream_sampled): N images with num_return samples each are a
+        queue of N * num_return sequences on `slots` decode rows -> (ids [N * num_return, max_length] padded with the pad id, lengths
+        [N * num_return], decode steps run[, token_scores [N * num_return, max_length - 1]]).  Row n * num_return + j is sample j of image
+        n and equals generate_sampled() on image n alone with stream id n * num_return + j (stream_ids [N * num_return] names other ids),
+        cut at its length.  One encoder pass and one pool entry per image."""
+        ids, bb, am, pv, N, L = self._inputs(input_ids, bbox, attention_mask, pixel_values)
+        nr = int(num_return)
+        if nr < 1:
+            raise ValueError(f"num_return must be >= 1, got {nr}")
+        if not float(temperature) > 0.0:
+            raise ValueError(f"temperature must be > 0, got {temperature}")
+        if int(top_k) < 0:
+            raise ValueError(f"top_k must be >= 0 (0 = off), got {top_k}")
+        if not 0.0 < float(top_p) <= 1.0:
+            raise ValueError(f"top_p must be in (0, 1], got {top_p}")
+        R = N * nr
+        need = C.c_size_t()
+        self._chk(self.lib.mg_stream_workspace_bytes(self.model, chunk, L, slots, pool_chunks, C.byref(need)))
+        if getattr(self, "_sws_bytes", 0) < need.value:
+            self._sws = None
+            self._sws = self.mem.empty((need.value,), np.uint8)
+            self._sws_bytes = need.value
+        # persistent output / stream-id buffers: the captured decode step holds their addresses
+        okey = ("stream-sampled", R, max_length)
+        c = self._gen_out.get(okey)
+        if c is None:
+            c = self._gen_out[okey] = {"ids": self.mem.empty((R, max_length), np.int64), "len": self.mem.empty((R,), np.int32),
+                                       "ts": self.mem.zeros((R, max_length - 1), np.float32), "sid": None, "sid_host": None}
+        sid = None
+        if stream_ids is not None:
+            host = np.ascontiguousarray(np.asarray(stream_ids).astype(np.uint64).reshape(-1))
+            if host.shape[0] != R:
+                raise ValueError(f"stream_ids must hold N * num_return = {R} ids, got {host.shape[0]}")
+            if c["sid_host"] is None or not np.array_equal(c["sid_host"], host):
+                c["sid"], c["sid_host"] = self.mem.asarray(host.view(np.int64), np.int64), host
+            sid = c["sid"]
+        opts = MgSampleOpts(float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                            self.mem.ptr(sid).value if sid is not None else None, nr,
+                            self.mem.ptr(c["ts"]).value if return_scores else None)
+        steps = C.c_long(0)
+        self._chk(self.lib.mg_generate_stream_sampled(
+            self.model, self.mem.stream(), self.mem.ptr(self._sws), self._sws_bytes, self.mem.ptr(ids), self.mem.ptr(bb),
+            self.mem.ptr(am) if am is not None else None, self.mem.ptr(pv), N, L, chunk, slots, pool_chunks, max_length, min_length,
+            self.mem.ptr(c["ids"]), self.mem.ptr(c["len"]), C.byref(steps), C.byref(opts)))
+        res = (self.mem.copy(c["ids"]), self.mem.copy(c["len"]), int(steps.value))
+        return res + (self.mem.copy(c["ts"]),) if return_scores else res
 
     def generate_stream_beam(self, input_ids, bbox, attention_mask, pixel_values, num_beams=5, max_length=512, min_length=0,
                              length_penalty=1.0, early_stopping=False, chunk=32, slots=32, pool_chunks=3, num_return=1, return_scores=False):

@@ -416,24 +416,11 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
             return (input_ids != pad).long()
         return torch.ones_like(input_ids)
 
-    def _generate_sampled(self, input_ids, bbox, pixel_values, attention_mask, num_beams, max_length, min_length, e1, num_return, as_dict,
-                          want_scores, want_logits, kw):
-        """generate(do_sample=True): stock `_sample` with the temperature / top-k / top-p warpers, drawn on the device
-        (include/mgrapher.h mg_generate_sampled).  temperature=1.0, top_k=None (generation_config.top_k if the model has one, else stock's
-        default 50; 0 = off), top_p=1.0, num_return_sequences=1, seed=None, stream_ids=None.
-        Reproducibility: seed=None draws the call's seed from torch's default CPU generator, so torch.manual_seed(s) makes a sequence of
-        calls reproducible and consecutive calls differ; an explicit seed is used as given.  A row's draws depend on (seed, its stream
-        id - by default its row index b * num_return_sequences + j - the column) and its own logits only.
-        -> [B * num_return_sequences, T], the samples of an image consecutive; return_dict_in_generate: GenerateOutput with token_scores
-        (the log-probability of every drawn token under the warped distribution).  output_logits: the raw logits of every step;
-        output_scores: those logits after MinLength and temperature (the top-k / top-p filters are applied inside the selection kernel and
-        are NOT reflected there).  Both go through the parity capture (eager launches, same ids)."""
+    def _sampling_options(self, num_beams, num_return, temperature, top_k, top_p, seed):
+        """Defaults and validation of do_sample=True, shared by generate() and generate_queue() -> (temperature, top_k, top_p, seed)."""
         if num_beams > 1:
             raise ValueError("`do_sample=True` with `num_beams` > 1 (beam-sample) is not built; use num_return_sequences for several samples.")
-        temperature = kw.pop("temperature", None)
         temperature = 1.0 if temperature is None else float(temperature)
-        top_k, top_p = kw.pop("top_k", None), kw.pop("top_p", None)
-        seed, stream_ids = kw.pop("seed", None), kw.pop("stream_ids", None)
         if top_k is None:
             top_k = getattr(getattr(self, "generation_config", None), "top_k", None)
             top_k = 50 if top_k is None else top_k
@@ -448,6 +435,23 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
             raise ValueError(f"`num_return_sequences` has to be >= 1, got {num_return}")
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        return temperature, int(top_k), top_p, int(seed)
+
+    def _generate_sampled(self, input_ids, bbox, pixel_values, attention_mask, num_beams, max_length, min_length, e1, num_return, as_dict,
+                          want_scores, want_logits, kw):
+        """generate(do_sample=True): stock `_sample` with the temperature / top-k / top-p warpers, drawn on the device
+        (include/mgrapher.h mg_generate_sampled).  temperature=1.0, top_k=None (generation_config.top_k if the model has one, else stock's
+        default 50; 0 = off), top_p=1.0, num_return_sequences=1, seed=None, stream_ids=None.
+        Reproducibility: seed=None draws the call's seed from torch's default CPU generator, so torch.manual_seed(s) makes a sequence of
+        calls reproducible and consecutive calls differ; an explicit seed is used as given.  A row's draws depend on (seed, its stream
+        id - by default its row index b * num_return_sequences + j - the column) and its own logits only.
+        -> [B * num_return_sequences, T], the samples of an image consecutive; return_dict_in_generate: GenerateOutput with token_scores
+        (the log-probability of every drawn token under the warped distribution).  output_logits: the raw logits of every step;
+        output_scores: those logits after MinLength and temperature (the top-k / top-p filters are applied inside the selection kernel and
+        are NOT reflected there).  Both go through the parity capture (eager launches, same ids)."""
+        stream_ids = kw.pop("stream_ids", None)
+        temperature, top_k, top_p, seed = self._sampling_options(num_beams, num_return, kw.pop("temperature", None), kw.pop("top_k", None),
+                                                                 kw.pop("top_p", None), kw.pop("seed", None))
         self._check_e1(e1)
         eng = self._eng()
         max_length = int(max_length or self.config.max_length)
@@ -562,7 +566,8 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
         return InFlight(self._eng(), n)
 
     def generate_queue(self, encodings, max_length=None, min_length=0, slots=32, chunk=32, contexts=1, num_beams=1, length_penalty=1.0,
-                       early_stopping=False, num_return_sequences=1, return_scores=False):
+                       early_stopping=False, num_return_sequences=1, return_scores=False, do_sample=False, temperature=None, top_k=None,
+                       top_p=None, seed=None):
         """The reference's evaluation loop (ref: utils/ocsr/utils_evaluation.py:140-285) as ONE call: `encodings` = the per-sample
         dicts it builds (input_ids [1, L_n] or [L_n], bbox, pixel_values; attention_mask / labels ignored as there), greedy,
         max_length as there.  Returns a list of 1-D id tensors - predictions[n] == self.generate(**encodings[n], num_beams=1,
@@ -576,8 +581,23 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
         return_scores or num_return_sequences > 1: one dict per image instead - "sequences" [num_return_sequences, T] (the n-best list,
         best first, T = the longest returned hypothesis' columns), "token_scores" [num_return_sequences, T - 1] (as generate()'s
         GenerateOutput.token_scores) and, for beam search, "sequences_scores" [num_return_sequences] and "beam_indices" (numbered as if
-        the image were decoded alone)."""
+        the image were decoded alone).
+        do_sample=True: the sampled queue (mg_generate_stream_sampled) - temperature / top_k / top_p / seed with generate(do_sample=True)'s
+        defaults and validation, num_beams > 1 refused, num_return_sequences = S samples per image (S * N sequences work through the
+        `slots` rows; one encoder pass per image).  predictions[n] == self.generate(**encodings[n], do_sample=True, seed=seed,
+        stream_ids=[n * S, ..., n * S + S - 1], num_return_sequences=S, ...) cut at each row's length: sample j of image n draws from
+        the random stream n * S + j whatever `slots`, `chunk` and `contexts` are.  S == 1 without return_scores: 1-D id tensors;
+        otherwise one dict per image, "sequences" [S, T] (T = the longest sample's columns, shorter ones padded) and "token_scores"
+        [S, T - 1] (the log-probability of each drawn token under the warped distribution)."""
         from .assembly import collate_for_generate
+        num_beams = int(num_beams)
+        nr = int(num_return_sequences or 1)
+        if do_sample:
+            temperature, top_k, top_p, seed = self._sampling_options(num_beams, nr, temperature, top_k, top_p, seed)
+        elif num_beams == 1 and nr > 1:
+            raise ValueError(f"Greedy methods without beam search do not support `num_return_sequences` different than 1 (got {nr}).")
+        if nr > num_beams and not do_sample:
+            raise ValueError("`num_return_sequences` has to be smaller or equal to `num_beams`.")
         self._check_e1(None)
         eng = self._eng()
         max_length = int(max_length or self.config.max_length)
@@ -588,19 +608,22 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
         batch = collate_for_generate(feats)
         pix = torch.cat([torch.as_tensor(e["pixel_values"]).reshape(1, *torch.as_tensor(e["pixel_values"]).shape[-3:]) for e in encodings]).to(self.device)
         n = len(feats)
-        num_beams = int(num_beams)
-        nr = int(num_return_sequences or 1)
-        if num_beams == 1 and nr > 1:
-            raise ValueError(f"Greedy methods without beam search do not support `num_return_sequences` different than 1 (got {nr}).")
-        if nr > num_beams:
-            raise ValueError("`num_return_sequences` has to be smaller or equal to `num_beams`.")
         scored = bool(return_scores) or nr > 1
         if num_beams > 1:
             slots = max(1, min(int(slots), 256 // num_beams))
+        elif do_sample:
+            slots = max(1, min(int(slots), 256))      # the engine's limit of live rows (slots count sequences here)
 
         def run(ctx, sl):
             m = sl.stop - sl.start
-            if num_beams > 1:
+            if do_sample:
+                # global stream ids: sequence (part start + i) * S + j, so the result does not depend on `contexts`
+                r = ctx.generate_stream_sampled(batch["input_ids"][sl], batch["bbox"][sl], batch["attention_mask"][sl], pix[sl],
+                                                max_length=max_length, min_length=int(min_length), temperature=temperature, top_k=top_k,
+                                                top_p=top_p, seed=seed, num_return=nr, stream_ids=np.arange(sl.start * nr, sl.stop * nr),
+                                                chunk=min(chunk, m), slots=min(slots, m * nr), pool_chunks=3, return_scores=scored)
+                o, l = r[0], r[1]
+            elif num_beams > 1:
                 r = ctx.generate_stream_beam(batch["input_ids"][sl], batch["bbox"][sl], batch["attention_mask"][sl], pix[sl],
                                              num_beams=num_beams, max_length=max_length, min_length=int(min_length),
                                              length_penalty=float(length_penalty), early_stopping=bool(early_stopping),
@@ -619,6 +642,12 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
             # o [m * nr, max_length]; the queue's beam indices number the rows of the part's images: renumbered as if each image were alone
             l = l.cpu().tolist()
             res = []
+            if do_sample:      # l [m * nr]: every sample has its own length
+                for i in range(len(l) // nr):
+                    rows = slice(i * nr, (i + 1) * nr)
+                    li = max(l[rows])
+                    res.append({"sequences": o[rows, :li], "token_scores": r[3][rows, :li - 1]})
+                return res
             for i, li in enumerate(l):
                 rows = slice(i * nr, (i + 1) * nr)
                 d = {"sequences": o[rows, :li]}
