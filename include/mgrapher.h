@@ -457,6 +457,48 @@ int mgk_sample_select(void* stream, const float* logits, int rows, int V, int ld
 /* The generator itself, on the host: out_host[4] = Philox4x32-10 with key = seed and counter = (stream_id lo, stream_id hi, pos, 0).
  * The draw uses r = out[1] << 32 | out[0]. */
 int mgk_philox(uint64_t seed, uint64_t stream_id, uint32_t pos, uint32_t* out_host);
+/* The selection step of a decode loop in every form the loops launch it in (test entries).  mgk_slot_table = SlotTable (csrc/mg_kernels.h):
+ * pos / img / pool [slots] i32, ctr [16] i32 ([0] live slots, [1] sequences done, [2] steps, [4] queue head, [5] images ready, [7] oldest
+ * live sequence), out_len [sequences of the queue]; first_tok [sequences] i64, nullable; stop[0 .. n_stop) the stop tokens slot_refill tests
+ * first_tok against; nsamp sequences per image.  pos null = no slot table (batch form).
+ * mgk_select_desc = ArgmaxArgs: fused = 0 greedy_select on logits [rows][ldl] (ldl a multiple of 4 >= V; batch form, or the queue form with
+ * slots.pos given, which needs img / ctr / out_len too); fused = 1 greedy_select_fused on the lm_head partials ptop [rows][ntiles] float4 /
+ * stopv [rows][4] (mgk_lm_head_step), which also writes h [rows][d] fp32, x_pk packed [rows padded to 32][d] and, if given, the window
+ * [x2_col0, x2_col0 + d) of x2_pk (x2_ld columns); d <= 2048, a multiple of 16; batch form only.  eos_more[0 .. n_eos_more) are further stop
+ * tokens; top2 [rows][2], or [max_len][rows][2] with pos_dev; step_ctr [8] i32 ([0] unfinished rows, [1] first all-finished step, [2] steps,
+ * [6] arrivals); token_scores [rows][ts_ld].  n_unfinished is NOT cleared by the call: the caller sets it (the step_ctr path clears it).
+ * 1 <= rows <= 256. */
+typedef struct mgk_slot_table {
+    int* pos; int* img; int* pool; int* ctr; int* out_len;
+    int pool_cap, start_id;
+    const int64_t* first_tok;
+    int n_stop, stop[4], max_len, nsamp;
+} mgk_slot_table;
+typedef struct mgk_select_desc {
+    int fused;
+    const float* logits; int rows, V, ldl;
+    int eos, pad, suppress_eos, n_eos_more, eos_more[3];
+    int64_t* next_ids; int64_t* out_ids; int max_len, pos;
+    const int* pos_dev;
+    int min_len;
+    int* unfinished; int* n_unfinished;
+    float* top2;
+    int* step_ctr;
+    mgk_slot_table slots;
+    const void* ptop; const float* stopv; int ntiles;
+    const void* tok_emb; float* h; const float* gain; void* x_pk; void* x2_pk; int x2_ld, x2_col0, d; float eps;
+    float* token_scores; int ts_ld;
+} mgk_select_desc;
+int mgk_select_ex(void* stream, const mgk_select_desc* s);
+/* mgk_sample_select in the queue form (SampleArgs::slots): row = slot, column slots.pos[row] + 1 of sequence slots.img[row]; stream_ids and
+ * token_scores are indexed by the sequence.  Arguments and checks of mgk_sample_select (`pos` and n_unfinished are not used by this form;
+ * n_unfinished is not cleared) plus the slot table, whose pos / img / ctr / out_len are required. */
+int mgk_sample_select_queue(void* stream, const float* logits, int rows, int V, int ldl, int eos, int pad, int min_len, float temperature,
+                            int top_k, float top_p, uint64_t seed, const uint64_t* stream_ids, int64_t* next_ids, int64_t* out_ids, int max_len,
+                            int pos, int* unfinished, int* n_unfinished, float* token_scores, int ts_ld, const mgk_slot_table* slots);
+/* slot_refill (csrc/k_decode.hip) after a selection: idle slots take the next ready sequences of the queue.  1 <= rows <= 256, nsamp >= 1,
+ * pool_cap >= 1. */
+int mgk_slot_refill(void* stream, const mgk_slot_table* slots, int64_t* next_ids, int* unfinished, int rows);
 
 /* ---- kernels of the OCSR vision branch "e1" (csrc/k_swin.hip; test entries, not on the product path) ---- */
 /* (Shifted-)window attention of one Swin block, head dim 32.  qkv_pk packed bf16 [B*R*R padded to 32][3C] = [q | k | v] in the natural token

@@ -324,6 +324,70 @@ int mgk_sample_select(void* stream, const float* logits, int rows, int V, int ld
     return MG_OK;
 }
 
+// The selection step in every form the decode loops launch it in (greedy_select batch / queue, greedy_select_fused, sample_select queue,
+// slot_refill): descriptors as mgk_gemm_resid_ex.  None of them clears n_unfinished (the engine does not either: the step_ctr path does).
+static SlotTable slot_table(const mgk_slot_table* t) {
+    SlotTable s{};
+    if (!t) return s;
+    s.pos = t->pos; s.img = t->img; s.pool = t->pool; s.ctr = t->ctr; s.out_len = t->out_len; s.pool_cap = t->pool_cap; s.start_id = t->start_id;
+    s.first_tok = t->first_tok; s.n_stop = t->n_stop; s.max_len = t->max_len; s.nsamp = t->nsamp;
+    for (int k = 0; k < 4; ++k) s.stop[k] = t->stop[k];
+    return s;
+}
+int mgk_select_ex(void* stream, const mgk_select_desc* s) {
+    if (!s || !s->next_ids || !s->out_ids || !s->unfinished) return MG_E_ARG;
+    const bool queue = s->slots.pos != nullptr;
+    if (s->fused && queue) return MG_E_ARG;                              // (the fused tail has no queue form)
+    if (queue ? (!s->slots.img || !s->slots.ctr || !s->slots.out_len) : !s->n_unfinished) return MG_E_ARG;
+    if (s->n_eos_more < 0 || s->n_eos_more > 3) return MG_E_ARG;
+    if (s->rows < 1 || s->rows > 256 || s->V < 1 || s->max_len < 1 || s->pos < 0) return MG_E_SHAPE;
+    if (s->token_scores && (s->ts_ld < s->max_len - 1 || (!queue && !s->pos_dev && s->pos < 1))) return MG_E_SHAPE;
+    if (s->fused) {
+        if (!s->ptop || !s->stopv || !s->tok_emb || !s->gain || !s->h || !s->x_pk) return MG_E_ARG;
+        if (s->d < 16 || s->d > 2048 || (s->d & 15) || s->ntiles != (s->V + 31) / 32) return MG_E_SHAPE;
+        if (s->pad < 0 || s->pad >= s->V) return MG_E_ARG;               // (a finished row embeds pad)
+        if (s->x2_pk && ((s->x2_ld & 15) || s->x2_col0 < 0 || (s->x2_col0 & 7) || s->x2_col0 + s->d > s->x2_ld)) return MG_E_SHAPE;
+    } else {
+        if (!s->logits) return MG_E_ARG;
+        if (s->ldl < s->V || (s->ldl & 3)) return MG_E_SHAPE;
+    }
+    ArgmaxArgs a{};
+    a.logits = s->logits; a.rows = s->rows; a.V = s->V; a.ldl = s->ldl; a.eos = s->eos; a.pad = s->pad; a.suppress_eos = s->suppress_eos;
+    a.n_eos_more = s->n_eos_more;
+    for (int k = 0; k < 3; ++k) a.eos_more[k] = s->eos_more[k];
+    a.next_ids = s->next_ids; a.out_ids = s->out_ids; a.max_len = s->max_len; a.pos = s->pos; a.pos_dev = s->pos_dev; a.min_len = s->min_len;
+    a.unfinished = s->unfinished; a.n_unfinished = s->n_unfinished; a.top2 = s->top2; a.step_ctr = s->step_ctr;
+    if (queue) a.slots = slot_table(&s->slots);
+    a.ptop = (const float4*)s->ptop; a.stopv = s->stopv; a.ntiles = s->ntiles; a.tok_emb = (const uint16_t*)s->tok_emb; a.h = s->h;
+    a.gain = s->gain; a.x_pk = (uint16_t*)s->x_pk; a.x2_pk = (uint16_t*)s->x2_pk; a.x2_ld = s->x2_ld; a.x2_col0 = s->x2_col0; a.d = s->d;
+    a.eps = s->eps; a.token_scores = s->token_scores; a.ts_ld = s->ts_ld;
+    if (s->fused) greedy_select_fused(a, (mgStream_t)stream); else greedy_select(a, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_sample_select_queue(void* stream, const float* logits, int rows, int V, int ldl, int eos, int pad, int min_len, float temperature,
+                            int top_k, float top_p, uint64_t seed, const uint64_t* stream_ids, int64_t* next_ids, int64_t* out_ids, int max_len,
+                            int pos, int* unfinished, int* n_unfinished, float* token_scores, int ts_ld, const mgk_slot_table* slots) {
+    if (!logits || !next_ids || !out_ids || !unfinished || !n_unfinished || rows < 1 || ldl < V || (ldl & 3)) return MG_E_ARG;
+    if (!(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f)) return MG_E_ARG;
+    if (!slots || !slots->pos || !slots->img || !slots->ctr || !slots->out_len) return MG_E_ARG;
+    if (rows > 256 || max_len < 1 || (token_scores && ts_ld < max_len - 1)) return MG_E_SHAPE;
+    if (!sample_select_supported(V)) return MG_E_UNSUPPORTED;
+    SampleArgs a{};
+    a.logits = logits; a.rows = rows; a.V = V; a.ldl = ldl; a.eos = eos; a.pad = pad; a.min_len = min_len;
+    a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.seed = seed; a.stream_ids = stream_ids;
+    a.next_ids = next_ids; a.out_ids = out_ids; a.max_len = max_len; a.pos = pos; a.unfinished = unfinished;
+    a.n_unfinished = n_unfinished; a.token_scores = token_scores; a.ts_ld = ts_ld; a.slots = slot_table(slots);
+    sample_select(a, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_slot_refill(void* stream, const mgk_slot_table* slots, int64_t* next_ids, int* unfinished, int rows) {
+    if (!slots || !slots->pos || !slots->img || !slots->pool || !slots->ctr || !slots->out_len || !next_ids || !unfinished) return MG_E_ARG;
+    if (slots->nsamp < 1 || slots->pool_cap < 1 || slots->n_stop < 0 || slots->n_stop > 4) return MG_E_ARG;
+    if (rows < 1 || rows > 256) return MG_E_SHAPE;                       // (the kernel keeps the slots' state in two LDS arrays of 256)
+    slot_refill(slot_table(slots), next_ids, unfinished, rows, (mgStream_t)stream);
+    return MG_OK;
+}
+
 // the generator of sample_select on the host: out_host[4] = Philox4x32-10(key = seed, counter = (stream_id lo, stream_id hi, pos, 0))
 int mgk_philox(uint64_t seed, uint64_t stream_id, uint32_t pos, uint32_t* out_host) {
     if (!out_host) return MG_E_ARG;
