@@ -3,6 +3,7 @@
 // Host code only orchestrates launches on the caller's stream; every byte of model arithmetic runs in HIP kernels.
 #include "mg_kernels.h"
 #include "mg_graph.h"
+#include "mg_switch.h"
 #include "../../include/mgrapher.h"
 
 #include <math.h>
@@ -687,7 +688,7 @@ static void decode_step(mg_model* m, const DecodeCtx& c, int t, const int* tdev,
     // tools build only (tools/whatif_decode.py: WRONG results, valid timing): launches of the step left out by bit - 1 QKV, 2 self-attention,
     // 4 [Wo | cross-Q], 8 cross-attention, 16 [Wxo | FFN-wi], 32 FFN-wo, 64 lm_head
 #ifdef MG_TOOLS
-    static const int whatif = [] { const char* e = getenv("MG_WHATIF_STEP"); return e ? atoi(e) : 0; }();
+    static const int whatif = env_int("MG_WHATIF_STEP", 0);
 #else
     constexpr int whatif = 0;
 #endif

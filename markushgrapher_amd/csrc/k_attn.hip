@@ -13,7 +13,8 @@
 // (double-buffered, fragment order, conflict-free b128 reads); per-key metadata (mask, box centres) and the
 // three bias tables of head h live in LDS for the whole workgroup.
 #include "mg_kernels.h"
-#include <atomic>
+#include "mg_dispatch.h"
+#include "mg_switch.h"
 
 namespace mg {
 
@@ -708,29 +709,26 @@ void row_tile_list(const uint8_t* kmask, int rows, int* list, int* count, mgStre
     MG_LAUNCH(row_tile_list_kernel, dim3(1), dim3(256), (size_t)(256 * sizeof(int)), stream, kmask, n_tiles, list, count);
 }
 
-static std::atomic<int> g_att_qt{-1};          // query tiles per wave of the encoder attention: -1 = MG_ATT_QT or the default (2); process-wide test / A-B switch
-void attention_set_qt(int qt) { g_att_qt = qt; }
+static Switch g_att_qt{"MG_ATT_QT", 1};          // query tiles per wave of the encoder attention; process-wide test / A-B switch (mg_switch.h)
+void attention_set_qt(int qt) { if (qt < 0) g_att_qt.reset(); else g_att_qt.set(qt); }
 
 void attention(const AttnArgs& a_in, mgStream_t stream) {
     AttnArgs a = a_in;
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = getenv("MG_ATT_DBG"); dbg = e ? atoi(e) : 0; }
+    static const int dbg = env_int("MG_ATT_DBG", 0);
     a.dbg = dbg;
     const int nqb = (a.Sq_cap + 127) / 128;
     const dim3 grid(a.B * a.H * nqb), block(256);
     const size_t sh = attn_smem(a);
     if (a.mode == ATT_ENC) {
         const int nqe = (a.Sq_cap + AE_QB - 1) / AE_QB;
-        static bool once = false;
-        if (!once) { MG_SET_MAX_SMEM((&attention_enc_kernel<0, 1>), AE_SMEM); once = true; }
+        MG_SET_MAX_SMEM_ONCE((&attention_enc_kernel<0, 1>), AE_SMEM);
 #ifdef MG_TOOLS      // what-if variants with WRONG results: tools builds only
-        static int xp = -1;
-        if (xp < 0) { const char* e = getenv("MG_ATT_EXP"); xp = e ? atoi(e) : 0; }
+        static const int xp = env_int("MG_ATT_EXP", 0);
         if (xp) {
-#define MG_AX(N) case N: { static bool o = false; if (!o) { MG_SET_MAX_SMEM(&attention_enc_kernel<N>, AE_SMEM); o = true; } \
-                           MG_LAUNCH(attention_enc_kernel<N>, dim3(a.B * a.H * nqe), dim3(512), (size_t)AE_SMEM, stream, a); } break;
-            switch (xp) { MG_AX(1) MG_AX(2) MG_AX(3) MG_AX(4) MG_AX(7) MG_AX(8) MG_AX(9) MG_AX(15) default: MG_AX(11) }
-#undef MG_AX
+            dispatch_epi<1, 2, 3, 4, 7, 8, 9, 15, 11>(xp, [&](auto XP) {      // (any other value: 11)
+                MG_SET_MAX_SMEM_ONCE(&attention_enc_kernel<decltype(XP)::value>, AE_SMEM);
+                MG_LAUNCH(attention_enc_kernel<decltype(XP)::value>, dim3(a.B * a.H * nqe), dim3(512), (size_t)AE_SMEM, stream, a);
+            });
             return;
         }
 #endif
@@ -739,11 +737,8 @@ void attention(const AttnArgs& a_in, mgStream_t stream) {
         // launch against 430 us for the 8-wave form at the benchmark shape (encoder 36.4 against 33.2 ms per batch on the same box): two
         // WAVES per SIMD hide the stage's dependent LDS -> MFMA -> exp2 latencies, two instruction streams inside one wave do not (the
         // near-diagonal branches are per tile and keep the scheduler from interleaving them).  Kept behind MG_ATT_QT=2 / mgk_set_attention_qt.
-        int qt = g_att_qt;
-        if (qt < 0) { const char* e = getenv("MG_ATT_QT"); qt = e ? atoi(e) : 1; g_att_qt = qt; }
-        if (qt == 2) {
-            static bool once2 = false;
-            if (!once2) { MG_SET_MAX_SMEM((&attention_enc_kernel<0, 2>), AE_SMEM); once2 = true; }
+        if (g_att_qt.get() == 2) {
+            MG_SET_MAX_SMEM_ONCE((&attention_enc_kernel<0, 2>), AE_SMEM);
             MG_LAUNCH((attention_enc_kernel<0, 2>), dim3(a.B * a.H * nqe), dim3(256), (size_t)AE_SMEM, stream, a);
         } else {
             MG_LAUNCH((attention_enc_kernel<0, 1>), dim3(a.B * a.H * nqe), dim3(512), (size_t)AE_SMEM, stream, a);
@@ -752,12 +747,10 @@ void attention(const AttnArgs& a_in, mgStream_t stream) {
     else {
         // bias-free attention over full rows of keys (the ChemicalOCR vision tower: 1024 patches per frame, no mask unless a frame is padded): the
         // encoder's second-form kernel without its bias path - 253 -> us per launch at 32 frames (profiles/r05_s_*); MG_ATT_PLAIN=0: the first form
-        static int plain = -1;
-        if (plain < 0) { const char* e = getenv("MG_ATT_PLAIN"); plain = e ? atoi(e) : 1; }
+        static const int plain = env_int("MG_ATT_PLAIN", 1);
         if (plain && !a.kmask && a.Sk == a.Sk_cap && a.Sq == a.Sq_cap && (a.Sk_cap & 63) == 0 && (a.Sq_cap % AE_QB) == 0 && (a.Sk_cap >> 6) <= AE_MAXST && !a.kst && !a.qbv) {
             const int nqe = a.Sq_cap / AE_QB;
-            static bool oncep = false;
-            if (!oncep) { MG_SET_MAX_SMEM((&attention_enc_kernel<0, 1, true>), AE_SMEM); oncep = true; }
+            MG_SET_MAX_SMEM_ONCE((&attention_enc_kernel<0, 1, true>), AE_SMEM);
             MG_LAUNCH((attention_enc_kernel<0, 1, true>), dim3(a.B * a.H * nqe), dim3(512), (size_t)AE_SMEM, stream, a);
             return;
         }

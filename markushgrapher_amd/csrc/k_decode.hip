@@ -2,6 +2,7 @@
 // token selection.  These are the HBM-bound kernels of the path: per step the cross-attention K/V of every image
 // (2*N_dec*d*S_x bf16 bytes per image) is streamed exactly once.
 #include "mg_kernels.h"
+#include "mg_dispatch.h"
 #include <mutex>
 
 namespace mg {
@@ -325,9 +326,9 @@ void attention_step(const AttnStepArgs& a, mgStream_t stream) {
     if (a.rope.qkv) {            // rotary self-attention step: H = key/value heads, group = query heads per key/value head
         const dim3 rgrid(a.rows * a.H);
         const size_t rsh = (size_t)8 * G * 8 * 10 * sizeof(float);
-#define MG_AR(GG) case GG: MG_LAUNCH((attn_step_kernel<GG, 8, false, false, true>), rgrid, dim3(8 * 64), rsh, stream, a, (long long*)nullptr); break;
-        switch (G) { MG_AR(1) MG_AR(2) MG_AR(3) MG_AR(4) MG_AR(6) MG_AR(8) default: break; }
-#undef MG_AR
+        dispatch_int<1, 2, 3, 4, 6, 8>(G, [&](auto GG) {
+            MG_LAUNCH((attn_step_kernel<decltype(GG)::value, 8, false, false, true>), rgrid, dim3(8 * 64), rsh, stream, a, (long long*)nullptr);
+        });
         return;
     }
     const int owners = (a.rows + G - 1) / G;
@@ -351,17 +352,12 @@ void attention_step(const AttnStepArgs& a, mgStream_t stream) {
     // images/s with four contexts, 107 -> 103 for a call alone - hence per context and off by default.  The residency is capped through
     // the LDS request (more than half a CU's 160 KB); same kernel, same bits.
     if (a.one_wg_per_cu && a.len && G == 1 && sh < AS_SHARED_LDS) sh = AS_SHARED_LDS;      // (attention_step_allow_shared ran when the setting was made)
-#define MG_AS(GG)                                                                                         \
-    case GG:                                                                                              \
-        if (a.len) MG_LAUNCH((attn_step_kernel<GG, 8, true>), grid, block, sh, stream, a, (long long*)nullptr);               \
-        else if (eight) MG_LAUNCH((attn_step_kernel<GG, 8, false>), grid, block, sh, stream, a, (long long*)nullptr);          \
-        else MG_LAUNCH((attn_step_kernel<GG, 4, false>), grid, block, sh, stream, a, (long long*)nullptr);                     \
-        break;
-    switch (G) {
-        MG_AS(1) MG_AS(2) MG_AS(3) MG_AS(4) MG_AS(5) MG_AS(6) MG_AS(7) MG_AS(8)
-        default: break;
-    }
-#undef MG_AS
+    dispatch_int<1, 2, 3, 4, 5, 6, 7, 8>(G, [&](auto GG_) {
+        constexpr int GG = decltype(GG_)::value;
+        if (a.len) MG_LAUNCH((attn_step_kernel<GG, 8, true>), grid, block, sh, stream, a, (long long*)nullptr);
+        else if (eight) MG_LAUNCH((attn_step_kernel<GG, 8, false>), grid, block, sh, stream, a, (long long*)nullptr);
+        else MG_LAUNCH((attn_step_kernel<GG, 4, false>), grid, block, sh, stream, a, (long long*)nullptr);
+    });
 }
 
 // Greedy selection (gen:2925-2937): argmax with lowest-index tie-break (torch.argmax), finished rows emit pad,

@@ -6,6 +6,8 @@
 //   * swapping the two MFMA operands transposes the accumulator for free, which lets each epilogue store
 //     16-byte chunks in the layout its consumer wants (packed rows, packed transposed, or row-major fp32).
 #include "k_gemm_epi.h"
+#include "mg_dispatch.h"
+#include "mg_switch.h"
 #include <atomic>
 
 namespace mg {
@@ -398,17 +400,15 @@ static void launch_xl(const GemmArgs& a, mgStream_t stream) {
     constexpr int BM = 64 * TI;
     const int nblk = ((a.M + BM - 1) / BM) * ((a.N + GX_N - 1) / GX_N);
     const size_t sh = (size_t)2 * (2 * TI + 8) * 4 * TILE_BYTES;
-    static bool once = false;
-    if (!once) { MG_SET_MAX_SMEM((&gemm_xl_kernel<EPI, TI>), sh); once = true; }
+    MG_SET_MAX_SMEM_ONCE((&gemm_xl_kernel<EPI, TI>), sh);
 #ifdef MG_TOOLS      // what-if variants with WRONG results: tools builds only (build.py tools), never in the product library
     if constexpr (EPI == EPI_PK && TI == 5) {          // timing experiments (see the kernel's XP parameter)
-        static int xp = -1;
-        if (xp < 0) { const char* e = getenv("MG_GEMM_EXP"); xp = e ? atoi(e) : 0; }
+        static const int xp = env_int("MG_GEMM_EXP", 0);
         if (xp) {
-#define MG_XP(N) case N: { static bool o = false; if (!o) { MG_SET_MAX_SMEM((&gemm_xl_kernel<EPI, TI, N>), sh); o = true; } \
-                             MG_LAUNCH((gemm_xl_kernel<EPI, TI, N>), dim3(nblk), dim3(512), sh, stream, a); } break;
-            switch (xp) { MG_XP(1) MG_XP(2) MG_XP(3) MG_XP(4) MG_XP(5) MG_XP(6) default: MG_XP(7) }
-#undef MG_XP
+            dispatch_epi<1, 2, 3, 4, 5, 6, 7>(xp, [&](auto XP) {      // (any other value: 7)
+                MG_SET_MAX_SMEM_ONCE((&gemm_xl_kernel<EPI, TI, decltype(XP)::value>), sh);
+                MG_LAUNCH((gemm_xl_kernel<EPI, TI, decltype(XP)::value>), dim3(nblk), dim3(512), sh, stream, a);
+            });
             return;
         }
     }
@@ -420,32 +420,28 @@ template <int EPI>
 static void launch_wide(const GemmArgs& a, mgStream_t stream) {
     const int nblk = ((a.M + GW_M - 1) / GW_M) * ((a.N + GW_N - 1) / GW_N);
     const size_t sh = (size_t)GW_STAGES * GW_STAGE_BYTES;
-    static bool once = false;
-    if (!once) { MG_SET_MAX_SMEM(&gemm_wide_kernel<EPI>, sh); once = true; }
+    MG_SET_MAX_SMEM_ONCE(&gemm_wide_kernel<EPI>, sh);
     MG_LAUNCH((gemm_wide_kernel<EPI>), dim3(nblk), dim3(512), sh, stream, a);
 }
 
 // 0: 128x128 two-stage kernel only; 1: + 256x128 three-stage kernel for M >= 256; 2: + 256x256 kernel wherever it fits;
 // 4: + 320x256; 5 / 6: persistent ping-pong kernel with 256- / 320-row tiles (k_gemm_pp.hip);
 // 3 (default): by shape = 6 where the ping-pong kernel applies, else 4
-// (the three test / A-B switches of this file are process-wide: atomics, so that a host thread of another execution context never reads a torn
+// (the test / A-B switches of this file are process-wide: mg_switch.h, so that a host thread of another execution context never reads a torn
 // value; they select among kernels with IDENTICAL results and are meant to be set while no call is running - see include/mgrapher.h)
-static std::atomic<int> g_gemm_variant{3};
-void gemm_set_variant(int v) { g_gemm_variant = v; }
+static Switch g_gemm_variant{"MG_GEMM_VARIANT", 3};      // (the variable: A/B runs)
+void gemm_set_variant(int v) { g_gemm_variant.set(v); }
 
-bool gemm_has_gelu_epilogue(int M, int N) { return g_gemm_variant >= 2 && M >= 320 && N >= GX_N; }
+bool gemm_has_gelu_epilogue(int M, int N) { return g_gemm_variant.get() >= 2 && M >= 320 && N >= GX_N; }
 
 void gemm(const GemmArgs& a, int epi, mgStream_t stream) {
-    static bool env_read = false;
-    if (!env_read) { env_read = true; if (const char* e = getenv("MG_GEMM_VARIANT")) g_gemm_variant = atoi(e); }   // A/B runs
-    const int gv = g_gemm_variant;          // one read per call (the switch is process-wide)
+    const int gv = g_gemm_variant.get();          // one read per call (the switch is process-wide)
     // default (3): the persistent ping-pong kernel with 320-row tiles where its shape rules hold (K % 128 == 0), measured against the
     // two-stage kernel at M = 40960 (us): QKV 292 -> 245, O 166 -> 156, wi 356 -> 301, wo 434 -> 396, cross-KV 154 -> 146 (profiles/r04_b_*)
     // Small problems (round 5: the ChemicalOCR prefill at M = 4096, N = 576; the last Swin stages): fewer 320 x 256 tiles than
     // CUs leave part of the chip idle (o_proj of the prefill: 32 workgroups, 80 us for 2.7 GFLOP) - they take the 256 x 128 / 128 x 128
     // kernels, whose grids are 2.5 - 5 x larger.  Every output element is the same k-ascending chain of MFMAs in all tile kernels.
-    static int small_env = -1;
-    if (small_env < 0) { const char* e = getenv("MG_GEMM_SMALL"); small_env = e ? atoi(e) : 256; if (small_env == 1) small_env = 256; }      // (the tile-count threshold: fewer 320 x 256 tiles than CUs; 0: off.  96 -> 256: OCSR branch at 32 images 10.55 -> 9.68 ms, OCR tower + prefill 17.99 -> 17.84 ms)
+    static const int small_env = [] { const int v = env_int("MG_GEMM_SMALL", 256); return v == 1 ? 256 : v; }();      // (the tile-count threshold: fewer 320 x 256 tiles than CUs; 0: off.  96 -> 256: OCSR branch at 32 images 10.55 -> 9.68 ms, OCR tower + prefill 17.99 -> 17.84 ms)
     const long tiles_xl = (long)((a.M + 319) / 320) * ((a.N + GX_N - 1) / GX_N);
     // (not for the main encoder's deferred-RMSNorm chain - gain / partial sums / row scales: its GEMMs of one geometry stay on ONE kernel family,
     //  with or without the live-row-tile list, so that the list changes no bits)
@@ -456,64 +452,26 @@ void gemm(const GemmArgs& a, int epi, mgStream_t stream) {
     if (!small && gv >= 2 && a.M >= 320 && a.N >= GX_N) {
         // measured at M = 40960 (PFLOP/s, 256x128 / 256x256 / 320x256): QKV 0.72 / 0.92 / 1.01, O 0.47 / 0.45 / 0.53,
         // wi 0.78 / 0.99 / 1.04, wo 0.73 / 0.69 / 0.80, cross-KV 0.97 / 1.10 / 1.09 -> the 320-row tile by default
-        const bool five = gv >= 3;
-        const bool four = gv == 2;
-        if (five) {
-            switch (epi) {
-                case EPI_F32_STORE: launch_xl<EPI_F32_STORE, 5>(a, stream); break;
-                case EPI_F32_RESID: launch_xl<EPI_F32_RESID, 5>(a, stream); break;
-                case EPI_PK_RELU: launch_xl<EPI_PK_RELU, 5>(a, stream); break;
-                case EPI_PK_GELU: launch_xl<EPI_PK_GELU, 5>(a, stream); break;
-                case EPI_PK: launch_xl<EPI_PK, 5>(a, stream); break;
-                case EPI_PK_BIAS: launch_xl<EPI_PK_BIAS, 5>(a, stream); break;
-                case EPI_PK_GELU_ERF: launch_xl<EPI_PK_GELU_ERF, 5>(a, stream); break;
-                case EPI_RESID_NORM: launch_xl<EPI_RESID_NORM, 5>(a, stream); break;
-                default: launch_xl<EPI_HEADS, 5>(a, stream); break;
-            }
-            return;
-        }
-        if (four) {
-            switch (epi) {
-                case EPI_F32_STORE: launch_xl<EPI_F32_STORE, 4>(a, stream); break;
-                case EPI_F32_RESID: launch_xl<EPI_F32_RESID, 4>(a, stream); break;
-                case EPI_PK_RELU: launch_xl<EPI_PK_RELU, 4>(a, stream); break;
-                case EPI_PK_GELU: launch_xl<EPI_PK_GELU, 4>(a, stream); break;
-                case EPI_PK: launch_xl<EPI_PK, 4>(a, stream); break;
-                case EPI_PK_BIAS: launch_xl<EPI_PK_BIAS, 4>(a, stream); break;
-                case EPI_PK_GELU_ERF: launch_xl<EPI_PK_GELU_ERF, 4>(a, stream); break;
-                case EPI_RESID_NORM: launch_xl<EPI_RESID_NORM, 4>(a, stream); break;
-                default: launch_xl<EPI_HEADS, 4>(a, stream); break;
-            }
-            return;
-        }
+        // epilogues of the 320- / 256-row kernel: every one of the tile kernels; any other id (EPI_PK_SWIGLU) is launched as EPI_HEADS
+        dispatch_int<5, 4>(gv >= 3 ? 5 : 4, [&](auto TI) {      // (gv == 2: the 256-row tile)
+            dispatch_epi<EPI_F32_STORE, EPI_F32_RESID, EPI_PK_RELU, EPI_PK_GELU, EPI_PK, EPI_PK_BIAS, EPI_PK_GELU_ERF, EPI_RESID_NORM, EPI_HEADS>(
+                epi, [&](auto E) { launch_xl<decltype(E)::value, decltype(TI)::value>(a, stream); });
+        });
+        return;
     }
     const long tiles_w = (long)((a.M + GW_M - 1) / GW_M) * ((a.N + GW_N - 1) / GW_N);
     if (gv >= 1 && a.M >= GW_M && !(small && tiles_w < 96)) {      // (fewer than 96 of the 256 x 128 tiles as well: the 128 x 128 kernel)
-        switch (epi) {
-            case EPI_F32_STORE: launch_wide<EPI_F32_STORE>(a, stream); break;
-            case EPI_F32_RESID: launch_wide<EPI_F32_RESID>(a, stream); break;
-            case EPI_PK_RELU: launch_wide<EPI_PK_RELU>(a, stream); break;
-            case EPI_PK: launch_wide<EPI_PK>(a, stream); break;
-            case EPI_PK_BIAS: launch_wide<EPI_PK_BIAS>(a, stream); break;
-            case EPI_PK_GELU_ERF: launch_wide<EPI_PK_GELU_ERF>(a, stream); break;
-            case EPI_RESID_NORM: launch_wide<EPI_RESID_NORM>(a, stream); break;
-            default: launch_wide<EPI_HEADS>(a, stream); break;
-        }
+        // epilogues of the 256 x 128 kernel: no EPI_PK_GELU (gemm_has_gelu_epilogue); it and any other id are launched as EPI_HEADS
+        dispatch_epi<EPI_F32_STORE, EPI_F32_RESID, EPI_PK_RELU, EPI_PK, EPI_PK_BIAS, EPI_PK_GELU_ERF, EPI_RESID_NORM, EPI_HEADS>(
+            epi, [&](auto E) { launch_wide<decltype(E)::value>(a, stream); });
         return;
     }
     const int nblk = ((a.M + GB_M - 1) / GB_M) * ((a.N + GB_N - 1) / GB_N);
     const dim3 grid(nblk), block(256);
     const size_t sh = 2 * GB_STAGE_BYTES;
-    switch (epi) {
-        case EPI_F32_STORE: MG_LAUNCH((gemm_big_kernel<EPI_F32_STORE>), grid, block, sh, stream, a); break;
-        case EPI_F32_RESID: MG_LAUNCH((gemm_big_kernel<EPI_F32_RESID>), grid, block, sh, stream, a); break;
-        case EPI_PK_RELU: MG_LAUNCH((gemm_big_kernel<EPI_PK_RELU>), grid, block, sh, stream, a); break;
-        case EPI_PK: MG_LAUNCH((gemm_big_kernel<EPI_PK>), grid, block, sh, stream, a); break;
-        case EPI_PK_BIAS: MG_LAUNCH((gemm_big_kernel<EPI_PK_BIAS>), grid, block, sh, stream, a); break;
-        case EPI_PK_GELU_ERF: MG_LAUNCH((gemm_big_kernel<EPI_PK_GELU_ERF>), grid, block, sh, stream, a); break;
-        case EPI_RESID_NORM: MG_LAUNCH((gemm_big_kernel<EPI_RESID_NORM>), grid, block, sh, stream, a); break;
-        default: MG_LAUNCH((gemm_big_kernel<EPI_HEADS>), grid, block, sh, stream, a); break;
-    }
+    // epilogues of the 128 x 128 kernel: as the 256 x 128 kernel's
+    dispatch_epi<EPI_F32_STORE, EPI_F32_RESID, EPI_PK_RELU, EPI_PK, EPI_PK_BIAS, EPI_PK_GELU_ERF, EPI_RESID_NORM, EPI_HEADS>(
+        epi, [&](auto E) { MG_LAUNCH((gemm_big_kernel<decltype(E)::value>), grid, block, sh, stream, a); });
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -530,14 +488,13 @@ void gemm(const GemmArgs& a, int epi, mgStream_t stream) {
 // Larger weights (the main decoder at beam search, 160 rows = 5 tiles, 6-18 MB per projection) do NOT split: one tile per workgroup
 // measured 61.7 -> 51.2 images/s and two groups of tiles 67.4 -> 60.5 (profiles/r02_rows_split_ab.txt) - the other groups' workgroups
 // pull the weight slice from HBM again instead of finding it in L2.
-static std::atomic<int> g_rows_split_mode{-1};      // -1: by weight size (default); 0: never; 1: always one tile per workgroup  (tests, A/B runs)
-void gemm_rows_set_split(int mode) { g_rows_split_mode = mode; }
+static Switch g_rows_split_mode{"MG_ROWS_SPLIT", -1};      // -1: by weight size (default); 0: never; 1: always one tile per workgroup  (tests, A/B runs)
+void gemm_rows_set_split(int mode) { g_rows_split_mode.set(mode); }
 static int rows_split_tiles(int mt, size_t weight_elems) {          // row tiles per workgroup; mt = no split
-    static bool env_read = false;
-    if (!env_read) { env_read = true; if (const char* e = getenv("MG_ROWS_SPLIT")) g_rows_split_mode = atoi(e); }
-    if (mt <= 1 || g_rows_split_mode == 0) return mt;
+    const int mode = g_rows_split_mode.get();
+    if (mt <= 1 || mode == 0) return mt;
     const bool small = weight_elems * sizeof(uint16_t) <= ((size_t)4 << 20);
-    return (g_rows_split_mode == 1 || (g_rows_split_mode < 0 && small)) ? 1 : mt;
+    return (mode == 1 || (mode < 0 && small)) ? 1 : mt;
 }
 template <int EPI>
 MG_DEV void shift_rows(GemmArgs& a, int rt) {
@@ -906,11 +863,14 @@ __global__ __launch_bounds__(NW * 64) void gemm_rows_split_kernel(GemmArgs a) {
 
 // half-tile projections with >= 3 row tiles taking both halves per workgroup (same bits): -1 = as the call asks (GemmArgs::both_halves: the
 // engine sets it on contexts that share the GPU - +2 % in flight, -2.5 % for a call alone), 0 never, 1 always (gemm_rows_set_ft2 / MG_ROWS_FT2)
-static int g_rows_ft2 = [] { const char* e = getenv("MG_ROWS_FT2"); return (e && (e[0] == '0' || e[0] == '1')) ? e[0] - '0' : -1; }();
-void gemm_rows_set_ft2(int mode) { g_rows_ft2 = mode < 0 ? -1 : (mode ? 1 : 0); }
-static bool rows_ft2(const GemmArgs& a) { return g_rows_ft2 < 0 ? a.both_halves != 0 : g_rows_ft2 != 0; }
+static Switch g_rows_ft2{"MG_ROWS_FT2", -1, [](const char* e, int def) { return (e[0] == '0' || e[0] == '1') ? e[0] - '0' : def; }};
+void gemm_rows_set_ft2(int mode) { g_rows_ft2.set(mode < 0 ? -1 : (mode ? 1 : 0)); }
+static bool rows_ft2(const GemmArgs& a) { const int m = g_rows_ft2.get(); return m < 0 ? a.both_halves != 0 : m != 0; }
+// EPI_PK_SWIGLU exists in the half-tile form alone (N % 16 == 0): its full-tile kernels are not instantiated
 template <int EPI>
 static void gemm_rows_mt(const GemmArgs& a, int mt, bool half, mgStream_t stream) {
+    constexpr bool HALF_ONLY = EPI == EPI_PK_SWIGLU;
+    if (HALF_ONLY) half = true;
     // half-tile projections (few workgroups, latency-bound): 8 waves split K so each wave's share is one load round
     const int NW = half ? 8 : 4;
     const int mts = rows_split_tiles(mt, (size_t)a.N * a.K);
@@ -920,7 +880,7 @@ static void gemm_rows_mt(const GemmArgs& a, int mt, bool half, mgStream_t stream
     const size_t sh = (size_t)NW * 16 * 64 * sizeof(float) + (size_t)32 * mt * sizeof(float);
     if (split) {
         if (half) MG_LAUNCH((gemm_rows_split_kernel<EPI, true, 8>), grid, block, sh, stream, a);
-        else MG_LAUNCH((gemm_rows_split_kernel<EPI, false, 4>), grid, block, sh, stream, a);
+        else if constexpr (!HALF_ONLY) MG_LAUNCH((gemm_rows_split_kernel<EPI, false, 4>), grid, block, sh, stream, a);
         return;
     }
     // from three row tiles on a half-tile workgroup takes both halves of its weight tile (rows_block16 FT = 2: half the activation
@@ -928,38 +888,16 @@ static void gemm_rows_mt(const GemmArgs& a, int mt, bool half, mgStream_t stream
     if constexpr (EPI == EPI_PK || EPI == EPI_PK_RELU || EPI == EPI_HEADS || EPI == EPI_F32_STORE) {
         if (half && mt >= 3 && rows_ft2(a) && (a.N % 32) == 0) {
             const dim3 grid2((a.N + 31) / 32);
-#define MG_GR2(MTV) case MTV: MG_LAUNCH((gemm_rows_kernel<EPI, MTV, true, 8, 2>), grid2, block, sh, stream, a); return;
-            switch (mt) { MG_GR2(3) MG_GR2(4) MG_GR2(5) MG_GR2(6) MG_GR2(7) MG_GR2(8) default: break; }
-#undef MG_GR2
+            if (dispatch_int<3, 4, 5, 6, 7, 8>(mt, [&](auto MT) {
+                    MG_LAUNCH((gemm_rows_kernel<EPI, decltype(MT)::value, true, 8, 2>), grid2, block, sh, stream, a);
+                }))
+                return;
         }
     }
-#define MG_GR(MTV)                                                                                   \
-    case MTV:                                                                                        \
-        if (half) MG_LAUNCH((gemm_rows_kernel<EPI, MTV, true, 8>), grid, block, sh, stream, a);      \
-        else MG_LAUNCH((gemm_rows_kernel<EPI, MTV, false, 4>), grid, block, sh, stream, a);          \
-        break;
-    switch (mt) {
-        MG_GR(1) MG_GR(2) MG_GR(3) MG_GR(4) MG_GR(5) MG_GR(6) MG_GR(7) MG_GR(8)
-        default: break;
-    }
-#undef MG_GR
-}
-
-// half-tile form only (epilogues that exist there alone)
-template <int EPI>
-static void gemm_rows_mt_half(const GemmArgs& a, int mt, mgStream_t stream) {
-    const int mts = rows_split_tiles(mt, (size_t)a.N * a.K);
-    const bool split = mts < mt;
-    const dim3 grid(((a.N + 31) / 32) * 2, split ? (mt + mts - 1) / mts : 1), block(8 * 64);
-    if (split) mt = mts;
-    const size_t sh = (size_t)8 * 16 * 64 * sizeof(float) + (size_t)32 * mt * sizeof(float);
-    if (split) { MG_LAUNCH((gemm_rows_split_kernel<EPI, true, 8>), grid, block, sh, stream, a); return; }
-#define MG_GR(MTV) case MTV: MG_LAUNCH((gemm_rows_kernel<EPI, MTV, true, 8>), grid, block, sh, stream, a); break;
-    switch (mt) {
-        MG_GR(1) MG_GR(2) MG_GR(3) MG_GR(4) MG_GR(5) MG_GR(6) MG_GR(7) MG_GR(8)
-        default: break;
-    }
-#undef MG_GR
+    dispatch_int<1, 2, 3, 4, 5, 6, 7, 8>(mt, [&](auto MT) {
+        if (half) MG_LAUNCH((gemm_rows_kernel<EPI, decltype(MT)::value, true, 8>), grid, block, sh, stream, a);
+        else if constexpr (!HALF_ONLY) MG_LAUNCH((gemm_rows_kernel<EPI, decltype(MT)::value, false, 4>), grid, block, sh, stream, a);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1638,8 +1576,8 @@ static std::atomic<int> g_resid_f16{1};
 // same projection in 12.1 us and a call alone 4 % faster (decode step 4.87 -> 4.68 ms, beam queue on one context 25.3 -> 26.5 images/s), but with four
 // contexts in flight the headline loses 1.3 % (147.5 -> 145.5): it writes and re-reads 10.5 MB of partial sums per launch, and in flight the bytes a
 // launch moves are what it costs.  Off by default as well.
-static std::atomic<int> g_rows_mt{0};
-void gemm_rows_set_mt(int on) { g_rows_mt = on; }
+static Switch g_rows_mt{"MG_ROWS_MT", 0};      // (the variable: A/B runs)
+void gemm_rows_set_mt(int on) { g_rows_mt.set(on); }
 void gemm_rows_set_resid_f16(int on) { g_resid_f16 = on; }
 void gemm_rows_resid(const ResidArgs& r, mgStream_t stream) {
     int mt = (r.M + 31) / 32;
@@ -1666,32 +1604,27 @@ void gemm_rows_resid(const ResidArgs& r, mgStream_t stream) {
         return;
     }
     // several row tiles, K-slab form: the chunks of the one-workgroup form's waves as workgroups (same bits; see gemm_rows_resid_mt_kernel)
-    { static bool env_read = false; if (!env_read) { env_read = true; if (const char* e = getenv("MG_ROWS_MT")) g_rows_mt = atoi(e); } }   // A/B runs
     // MG_ROWS_MT_ALONE=1: a call that has the GPU to itself (ResidArgs::alone: no other execution context in flight) takes the two-launch K-slab form
     // from 4 row tiles on.  The launch is 23 % (160 rows) to 35 % (256 rows) faster back to back, but inside a decode step the gain is 0.5 - 3.5 % of
     // the step depending on the box and the cross-attention launch of the same call was timed 7 % slower beside it (103 -> 111 us, profiles/r05_e_*):
     // off by default.
-    static int alone_env = -1;
-    if (alone_env < 0) { const char* e = getenv("MG_ROWS_MT_ALONE"); alone_env = e ? atoi(e) : 0; }
-    const int rows_mt = g_rows_mt ? g_rows_mt.load() : ((r.alone && alone_env && mt >= 4) ? 2 : 0);
+    static const int alone_env = env_int("MG_ROWS_MT_ALONE", 0);
+    const int rows_mt_set = g_rows_mt.get();
+    const int rows_mt = rows_mt_set ? rows_mt_set : ((r.alone && alone_env && mt >= 4) ? 2 : 0);
     if (r.kpart && r.ticket && mt >= 2 && !split && (r.N & 255) == 0 && rows_mt) {
         const int NWf = wide ? 16 : 8, kp = r.K >> 5, per = (kp + NWf - 1) / NWf;
         if (per * NWf == kp && (per == 8 || per == 4 || per == 2)) {
             const int S = NWf;
-            static int fmode = -1;
-            if (fmode < 0) { const char* e = getenv("MG_MT_FENCE"); fmode = e ? atoi(e) : 0; }
+            static const int fmode = env_int("MG_MT_FENCE", 0);
             const dim3 gridk((r.N / 32) * S), blockk(64 * mt);
             const size_t shk = (size_t)32 * mt * sizeof(float) + 16;
             const bool two = rows_mt == 2 && S <= 16;              // two-launch variant: partial sums, then a chip-wide merge launch
             const int fm = two ? 6 : fmode;
-#define MG_RMT(MTV)                                                                                   \
-    case MTV:                                                                                         \
-        if (per == 8) MG_LAUNCH((gemm_rows_resid_mt_kernel<MTV, 8>), gridk, blockk, shk, stream, r, S, fm);       \
-        else if (per == 4) MG_LAUNCH((gemm_rows_resid_mt_kernel<MTV, 4>), gridk, blockk, shk, stream, r, S, fm);  \
-        else MG_LAUNCH((gemm_rows_resid_mt_kernel<MTV, 2>), gridk, blockk, shk, stream, r, S, fm);                \
-        break;
-            switch (mt) { MG_RMT(2) MG_RMT(3) MG_RMT(4) MG_RMT(5) MG_RMT(6) MG_RMT(7) MG_RMT(8) default: break; }
-#undef MG_RMT
+            dispatch_int<2, 3, 4, 5, 6, 7, 8>(mt, [&](auto MT) {
+                dispatch_int<8, 4, 2>(per, [&](auto PER) {
+                    MG_LAUNCH((gemm_rows_resid_mt_kernel<decltype(MT)::value, decltype(PER)::value>), gridk, blockk, shk, stream, r, S, fm);
+                });
+            });
             if (two) MG_LAUNCH(gemm_rows_resid_merge_kernel, dim3(r.N / 32, mt), dim3(256), 32 * sizeof(float), stream, r, S, 32 * mt);
             return;
         }
@@ -1703,18 +1636,13 @@ void gemm_rows_resid(const ResidArgs& r, mgStream_t stream) {
     // grid.y (a workgroup pulls its rows and the weight slice through ONE CU's 64 B/clk: 1.1 MB at 128 rows) - alone the launch drops
     // from 20.5 to 12.9 (groups of 2 tiles) / 8.8 us (1 tile), with four contexts in flight the run is SLOWER (142.1 -> 141.2 / 137.6
     // images/s): in flight the bytes moved through L2 count, not a launch's latency, and the groups re-read the weight slice.
-#define MG_RR(MTV)                                                                                 \
-    case MTV:                                                                                      \
-        if (f16 && wide) MG_LAUNCH((gemm_rows_resid_kernel<MTV, 16, true>), grid16, block, sh, stream, r);   \
-        else if (f16) MG_LAUNCH((gemm_rows_resid_kernel<MTV, 8, true>), grid16, block, sh, stream, r);       \
-        else if (wide) MG_LAUNCH((gemm_rows_resid_kernel<MTV, 16>), grid, block, sh, stream, r);   \
-        else MG_LAUNCH((gemm_rows_resid_kernel<MTV, 8>), grid, block, sh, stream, r);              \
-        break;
-    switch (mt) {
-        MG_RR(1) MG_RR(2) MG_RR(3) MG_RR(4) MG_RR(5) MG_RR(6) MG_RR(7) MG_RR(8)
-        default: break;
-    }
-#undef MG_RR
+    dispatch_int<1, 2, 3, 4, 5, 6, 7, 8>(mt, [&](auto MT) {
+        constexpr int MTV = decltype(MT)::value;
+        if (f16 && wide) MG_LAUNCH((gemm_rows_resid_kernel<MTV, 16, true>), grid16, block, sh, stream, r);
+        else if (f16) MG_LAUNCH((gemm_rows_resid_kernel<MTV, 8, true>), grid16, block, sh, stream, r);
+        else if (wide) MG_LAUNCH((gemm_rows_resid_kernel<MTV, 16>), grid, block, sh, stream, r);
+        else MG_LAUNCH((gemm_rows_resid_kernel<MTV, 8>), grid, block, sh, stream, r);
+    });
 }
 void gemm_rows_resid(const uint16_t* X, const uint16_t* W, float* h, const float* gain, float gscale, uint16_t* x_pk, float* part,
                      int M, int N, int K, const RowScale& rs, mgStream_t stream) {
@@ -1762,26 +1690,23 @@ void gemm_rows_pair(const ResidArgs& r, const GemmArgs& g, int epi, mgStream_t s
     const int nres = f16 ? r.N / 16 : r.N / 8, nrows = ((g.N + 31) / 32) * ((full || ft2) ? 1 : 2);
     const dim3 grid(nres + nrows), block(512);
     const size_t sh = (size_t)8 * 16 * 64 * sizeof(float) + (size_t)32 * mt * sizeof(float);
-    if (ft2) {
-#define MG_RPF(MTV) case MTV: MG_LAUNCH((gemm_rows_pair_kernel<EPI_HEADS, MTV, true, true, 2>), grid, block, sh, stream, r, g, nres); return;
-        switch (mt) { MG_RPF(3) MG_RPF(4) MG_RPF(5) MG_RPF(6) MG_RPF(7) MG_RPF(8) default: break; }
-#undef MG_RPF
-    }
-#define MG_RP2(MTV, FV)                                                                                              \
-        if (epi == EPI_PK_RELU && full) MG_LAUNCH((gemm_rows_pair_kernel<EPI_PK_RELU, MTV, false, FV>), grid, block, sh, stream, r, g, nres); \
-        else if (epi == EPI_PK_RELU) MG_LAUNCH((gemm_rows_pair_kernel<EPI_PK_RELU, MTV, true, FV>), grid, block, sh, stream, r, g, nres); \
-        else if (epi == EPI_F32_STORE) MG_LAUNCH((gemm_rows_pair_kernel<EPI_F32_STORE, MTV, true, FV>), grid, block, sh, stream, r, g, nres); \
-        else MG_LAUNCH((gemm_rows_pair_kernel<EPI_HEADS, MTV, true, FV>), grid, block, sh, stream, r, g, nres);
-#define MG_RP(MTV)                                                                                                   \
-    case MTV:                                                                                                        \
-        if (f16) { MG_RP2(MTV, true) } else { MG_RP2(MTV, false) }                                                   \
-        break;
-    switch (mt) {
-        MG_RP(1) MG_RP(2) MG_RP(3) MG_RP(4) MG_RP(5) MG_RP(6) MG_RP(7) MG_RP(8)
-        default: break;
-    }
-#undef MG_RP2
-#undef MG_RP
+    if (ft2 && dispatch_int<3, 4, 5, 6, 7, 8>(mt, [&](auto MT) {
+            MG_LAUNCH((gemm_rows_pair_kernel<EPI_HEADS, decltype(MT)::value, true, true, 2>), grid, block, sh, stream, r, g, nres);
+        }))
+        return;
+    // second projection: EPI_PK_RELU in the full- and the half-tile form, EPI_F32_STORE and (every other id) EPI_HEADS in the half-tile form
+    dispatch_int<1, 2, 3, 4, 5, 6, 7, 8>(mt, [&](auto MT) {
+        auto launch = [&](auto F16) {
+            constexpr int MTV = decltype(MT)::value;
+            constexpr bool FV = decltype(F16)::value;
+            if (epi == EPI_PK_RELU && full) MG_LAUNCH((gemm_rows_pair_kernel<EPI_PK_RELU, MTV, false, FV>), grid, block, sh, stream, r, g, nres);
+            else if (epi == EPI_PK_RELU) MG_LAUNCH((gemm_rows_pair_kernel<EPI_PK_RELU, MTV, true, FV>), grid, block, sh, stream, r, g, nres);
+            else if (epi == EPI_F32_STORE) MG_LAUNCH((gemm_rows_pair_kernel<EPI_F32_STORE, MTV, true, FV>), grid, block, sh, stream, r, g, nres);
+            else MG_LAUNCH((gemm_rows_pair_kernel<EPI_HEADS, MTV, true, FV>), grid, block, sh, stream, r, g, nres);
+        };
+        if (f16) launch(std::true_type{});
+        else launch(std::false_type{});
+    });
 }
 
 // fp32 helpers for product weights (finalize time, not on the hot path)
@@ -1859,25 +1784,16 @@ void gemm_rows_splitk(const uint16_t* X, const uint16_t* W, float* P, int M, int
     const int mt = (M + 31) / 32;
     const dim3 grid(((N + 31) / 32) * KS), block(256);
     const size_t sh = (size_t)4 * 16 * 64 * sizeof(float) + (size_t)32 * mt * sizeof(float) + (top.ptop ? (size_t)4 * 8 * 33 * sizeof(float) : 0);
-    switch (mt) {
-        case 1: MG_LAUNCH((gemm_rows_splitk_kernel<1>), grid, block, sh, stream, X, W, P, M, N, K, ldp, slab_stride, KS, rs, top); break;
-        case 2: MG_LAUNCH((gemm_rows_splitk_kernel<2>), grid, block, sh, stream, X, W, P, M, N, K, ldp, slab_stride, KS, rs, top); break;
-        case 3: MG_LAUNCH((gemm_rows_splitk_kernel<3>), grid, block, sh, stream, X, W, P, M, N, K, ldp, slab_stride, KS, rs, top); break;
-        case 4: MG_LAUNCH((gemm_rows_splitk_kernel<4>), grid, block, sh, stream, X, W, P, M, N, K, ldp, slab_stride, KS, rs, top); break;
-        case 5: MG_LAUNCH((gemm_rows_splitk_kernel<5>), grid, block, sh, stream, X, W, P, M, N, K, ldp, slab_stride, KS, rs, top); break;
-        case 6: MG_LAUNCH((gemm_rows_splitk_kernel<6>), grid, block, sh, stream, X, W, P, M, N, K, ldp, slab_stride, KS, rs, top); break;
-        case 7: MG_LAUNCH((gemm_rows_splitk_kernel<7>), grid, block, sh, stream, X, W, P, M, N, K, ldp, slab_stride, KS, rs, top); break;
-        case 8: MG_LAUNCH((gemm_rows_splitk_kernel<8>), grid, block, sh, stream, X, W, P, M, N, K, ldp, slab_stride, KS, rs, top); break;
-        default: break;
-    }
+    dispatch_int<1, 2, 3, 4, 5, 6, 7, 8>(mt, [&](auto MT) {
+        MG_LAUNCH((gemm_rows_splitk_kernel<decltype(MT)::value>), grid, block, sh, stream, X, W, P, M, N, K, ldp, slab_stride, KS, rs, top);
+    });
 }
 
 void gemm_rows(const GemmArgs& a_in, int epi, mgStream_t stream) {
 #ifdef MG_TOOLS      // what-if variants with WRONG results (tools build only): MG_WHATIF_KV = 1: the per-head projection does not append K / V to the
     GemmArgs a = a_in;   // cache; 2: it appends them at position 0 whatever the step
     {
-        static int wi = -1;
-        if (wi < 0) { const char* e = getenv("MG_WHATIF_KV"); wi = e ? atoi(e) : 0; }
+        static const int wi = env_int("MG_WHATIF_KV", 0);
         if (wi && epi == EPI_HEADS) {
             for (int ri = 0; ri < 3; ++ri)
                 if (a.heads.fmt[ri] == HF_STEP_KV) {
@@ -1896,15 +1812,14 @@ void gemm_rows(const GemmArgs& a_in, int epi, mgStream_t stream) {
     }
     // projections with few feature tiles get one workgroup per 16 features (packed / per-head epilogues only)
     const bool half = (epi == EPI_PK_RELU || epi == EPI_PK || epi == EPI_HEADS) && ((a.N + 31) / 32) < 256 && (a.N % 16) == 0;
-    switch (epi) {
-        case EPI_F32_STORE:      // few feature tiles, no bias, 16-byte aligned rows: the half-tile form (twice the workgroups, 8 waves splitting K)
-            gemm_rows_mt<EPI_F32_STORE>(a, mt, !a.bias && ((a.N + 31) / 32) < 128 && (a.N % 16) == 0 && (a.ldo % 4) == 0, stream); break;
-        case EPI_F32_RESID: gemm_rows_mt<EPI_F32_RESID>(a, mt, false, stream); break;
-        case EPI_PK_RELU: gemm_rows_mt<EPI_PK_RELU>(a, mt, half, stream); break;
-        case EPI_PK: gemm_rows_mt<EPI_PK>(a, mt, half, stream); break;
-        case EPI_PK_SWIGLU: gemm_rows_mt_half<EPI_PK_SWIGLU>(a, mt, stream); break;      // N % 16 == 0
-        default: gemm_rows_mt<EPI_HEADS>(a, mt, half, stream); break;
-    }
+    // EPI_F32_STORE with few feature tiles, no bias, 16-byte aligned rows: the half-tile form (twice the workgroups, 8 waves splitting K)
+    const bool half_f32 = !a.bias && ((a.N + 31) / 32) < 128 && (a.N % 16) == 0 && (a.ldo % 4) == 0;
+    // epilogues of the rows form: the only family with EPI_PK_SWIGLU (half-tile form alone, N % 16 == 0); no EPI_PK_BIAS, EPI_PK_GELU, EPI_PK_GELU_ERF,
+    // EPI_RESID_NORM - they and any other id are launched as EPI_HEADS
+    dispatch_epi<EPI_F32_STORE, EPI_F32_RESID, EPI_PK_RELU, EPI_PK, EPI_PK_SWIGLU, EPI_HEADS>(epi, [&](auto E) {
+        constexpr int EPI = decltype(E)::value;
+        gemm_rows_mt<EPI>(a, mt, EPI == EPI_F32_STORE ? half_f32 : EPI == EPI_F32_RESID ? false : half, stream);
+    });
 }
 
 }  // namespace mg

@@ -1,8 +1,8 @@
 // bf16 MFMA GEMM for the encoder-sized shapes: persistent workgroups, ping-pong wave schedule (see the kernel's header comment).
 // Operands, epilogues and results are those of gemm_xl_kernel (k_gemm.hip); gemm() dispatches here by variant.
 #include "k_gemm_epi.h"
-
-#include <atomic>
+#include "mg_dispatch.h"
+#include "mg_switch.h"
 
 namespace mg {
 
@@ -312,17 +312,15 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs a) {
     }
 }
 // row tiles of one problem over several launches: -1 = MG_PP_PARTS or 0; 0 never (fall back to the two-stage kernel: the default), 1 when the tile table is too small, 2 .. 8: always that many (tests)
-static std::atomic<int> g_pp_parts{-1};
-void gemm_pp_set_parts(int mode) { g_pp_parts = mode; }
+static Switch g_pp_parts{"MG_PP_PARTS", 0};      // (the variable: A/B runs)
+void gemm_pp_set_parts(int mode) { if (mode < 0) g_pp_parts.reset(); else g_pp_parts.set(mode); }
 
 template <int EPI, int TI>
 static bool launch_pp(const GemmArgs& a_in, mgStream_t stream) {
     GemmArgs a = a_in;
-    static int balance = -1;
-    if (balance < 0) { const char* e = getenv("MG_PP_BALANCE"); balance = e ? atoi(e) : 1; }      // (A/B runs)
+    static const int balance = env_int("MG_PP_BALANCE", 1);      // (A/B runs)
     a.pp_balance = balance;
-    static int colgroup = -1;
-    if (colgroup < 0) { const char* e = getenv("MG_PP_COLGROUP"); colgroup = e ? atoi(e) : 4; }      // (A/B runs; 0: linear order.  4 column tiles: FFN-wi 316 -> 299 us, encoder 35.9 -> 35.4 ms; 2: slower)
+    static const int colgroup = env_int("MG_PP_COLGROUP", 4);      // (A/B runs; 0: linear order.  4 column tiles: FFN-wi 316 -> 299 us, encoder 35.9 -> 35.4 ms; 2: slower)
     a.pp_colgroup = colgroup;
     constexpr int BM = 64 * TI;
     const int nblk = ((a.M + BM - 1) / BM) * ((a.N + GX_N - 1) / GX_N);
@@ -338,8 +336,7 @@ static bool launch_pp(const GemmArgs& a_in, mgStream_t stream) {
     // more tiles per workgroup than the kernel's tile table holds (balanced blocks are up to 30 % more; the FFN input projection of a 160-image
     // call: 10240 tiles): the row tiles in `parts` launches (every output tile is the same arithmetic whichever launch computes it)
     int parts = 1;
-    int mode = g_pp_parts.load();
-    if (mode < 0) { const char* e = getenv("MG_PP_PARTS"); mode = e ? atoi(e) : 0; g_pp_parts = mode; }      // (A/B runs)
+    const int mode = g_pp_parts.get();
     // Measured (profiles/r05_o_pp_parts_ab.txt, headline regime, same box, two runs each): FFN-wi of the 160-image calls as two launches of this
     // kernel against one launch of the two-stage kernel: encoder phase 190.3 against 189.1 ms per call, 147.1 against 146.8 images/s - no
     // difference, so the default stays 0 (such problems go to the two-stage kernel).
@@ -350,17 +347,15 @@ static bool launch_pp(const GemmArgs& a_in, mgStream_t stream) {
     if ((size_t)((a.M + 31) / 32) * 32 * (size_t)a.K * 2 > 0x7fffffffull || (size_t)((a.N + 31) / 32) * 32 * (size_t)a.K * 2 > 0x7fffffffull) return false;
     const size_t sh = (size_t)GP_RING * (2 * TI + 8) * TILE_BYTES + (size_t)GP_MAXT * (2 * TI + 2) * sizeof(int) +
                       (EPI == EPI_RESID_NORM ? (size_t)GP_GAIN_MAX * sizeof(float) : 0);
-    static bool once = false;
-    if (!once) { MG_SET_MAX_SMEM((&gemm_pp_kernel<EPI, TI>), sh); once = true; }
+    MG_SET_MAX_SMEM_ONCE((&gemm_pp_kernel<EPI, TI>), sh);
 #ifdef MG_TOOLS      // what-if variants with WRONG results: tools builds only
     if constexpr (EPI == EPI_PK || EPI == EPI_F32_RESID) {
-        static int xp = -1;
-        if (xp < 0) { const char* e = getenv("MG_PP_EXP"); xp = e ? atoi(e) : 0; }
+        static const int xp = env_int("MG_PP_EXP", 0);
         if (xp) {
-#define MG_PX(N) case N: { static bool o = false; if (!o) { MG_SET_MAX_SMEM((&gemm_pp_kernel<EPI, TI, N>), sh); o = true; } \
-                             MG_LAUNCH((gemm_pp_kernel<EPI, TI, N>), dim3(G), dim3(512), sh, stream, a); } break;
-            switch (xp) { MG_PX(1) MG_PX(2) MG_PX(3) MG_PX(4) MG_PX(7) MG_PX(8) MG_PX(9) MG_PX(11) default: MG_PX(15) }
-#undef MG_PX
+            dispatch_epi<1, 2, 3, 4, 7, 8, 9, 11, 15>(xp, [&](auto XP) {      // (any other value: 15)
+                MG_SET_MAX_SMEM_ONCE((&gemm_pp_kernel<EPI, TI, decltype(XP)::value>), sh);
+                MG_LAUNCH((gemm_pp_kernel<EPI, TI, decltype(XP)::value>), dim3(G), dim3(512), sh, stream, a);
+            });
             return true;
         }
     }
@@ -374,17 +369,11 @@ static bool launch_pp(const GemmArgs& a_in, mgStream_t stream) {
 }
 template <int TI>
 static bool launch_pp_epi(const GemmArgs& a, int epi, mgStream_t stream) {
-    switch (epi) {
-        case EPI_F32_STORE: return launch_pp<EPI_F32_STORE, TI>(a, stream);
-        case EPI_F32_RESID: return launch_pp<EPI_F32_RESID, TI>(a, stream);
-        case EPI_PK_RELU: return launch_pp<EPI_PK_RELU, TI>(a, stream);
-        case EPI_PK_GELU: return launch_pp<EPI_PK_GELU, TI>(a, stream);
-        case EPI_PK: return launch_pp<EPI_PK, TI>(a, stream);
-        case EPI_PK_BIAS: return launch_pp<EPI_PK_BIAS, TI>(a, stream);
-        case EPI_PK_GELU_ERF: return launch_pp<EPI_PK_GELU_ERF, TI>(a, stream);
-        case EPI_RESID_NORM: return launch_pp<EPI_RESID_NORM, TI>(a, stream);
-        default: return launch_pp<EPI_HEADS, TI>(a, stream);
-    }
+    // epilogues of the ping-pong kernel: those of gemm_xl_kernel; any other id (EPI_PK_SWIGLU) is launched as EPI_HEADS
+    bool launched = false;
+    dispatch_epi<EPI_F32_STORE, EPI_F32_RESID, EPI_PK_RELU, EPI_PK_GELU, EPI_PK, EPI_PK_BIAS, EPI_PK_GELU_ERF, EPI_RESID_NORM, EPI_HEADS>(
+        epi, [&](auto E) { launched = launch_pp<decltype(E)::value, TI>(a, stream); });
+    return launched;
 }
 
 // Measured and rejected (profiles/r04_h_gemm_coresident_rejected.txt): the TI = 4 form compiled to <= 192 registers per lane

@@ -7,6 +7,7 @@
 // Round-2 form: every operation its own launch, fp32 intermediates between GEMM and activation, eager decode steps.
 #include "mg_kernels.h"
 #include "mg_graph.h"
+#include "mg_switch.h"
 #include "mg_ocr.h"
 #include "mg_swin.h"
 #include "../../include/mgrapher.h"
@@ -186,8 +187,7 @@ void image_features(const mg_ocr_model* m, const Ws& w, const float* pix, const 
     // the batched 16-byte residual epilogue (EPI_RESID_NORM without gain; the row-major read-modify-write epilogue was 273 us per launch
     // at 32 pages), LayerNorm on the tile-wise kernel of the OCSR branch (512-byte runs; constant-one column and the bias hand-off as
     // before).  Widths that kernel is not instantiated for keep the first form.  MG_OCR_TILED=0: first form (A/B runs; same operations).
-    static int tiled_env = -1;
-    if (tiled_env < 0) { const char* e = getenv("MG_OCR_TILED"); tiled_env = e ? atoi(e) : 1; }
+    static const int tiled_env = env_int("MG_OCR_TILED", 1);
     const bool tiled = tiled_env && (MV % 32) == 0 && (vh == 64 || vh == 128 || vh == 256 || vh == 512 || vh == 768 || vh == 1024);
     auto layer_norm = [&](bool first, const float* wt, const float* bs, const float* add_bias, uint16_t* x_pk, float* out_f32, int Kaug) {
         if (!tiled) { ocr_layernorm_pack(w.vh, wt, bs, add_bias, x_pk, out_f32, MV, vh, Kaug, c.v_eps, st); return; }
@@ -249,8 +249,7 @@ void prefill(const mg_ocr_model* m, const Ws& w, const int64_t* ids, const float
     // Second form (round 5): the residual stream of the prefill in the TILED fp32 layout (w.ht) - o_proj / down_proj on the batched residual
     // epilogue instead of the row-major read-modify-write one, RMSNorm from 512-byte runs; the row-major copy w.h (what the callers read the
     // last positions from) is restored at the end.  MG_OCR_TILED=0: first form.
-    static int tiled_env = -1;
-    if (tiled_env < 0) { const char* e = getenv("MG_OCR_TILED"); tiled_env = e ? atoi(e) : 1; }
+    static const int tiled_env = env_int("MG_OCR_TILED", 1);
     const bool tiled = tiled_env && (td % 32) == 0;
     if (tiled) ocr_tile_f32(w.h, w.ht, MT, td, 1, st);
     auto norm = [&](const float* gain) {
