@@ -10,6 +10,10 @@
  *   mg_encode + mg_decoder_forward
  *                       replace   model(**sample).logits (teacher-forced forward)
  *                                 /root/reference/markushgrapher/core/trainers/curriculumTrainer.py:654-656
+ *   mg_encode + mg_decoder_score
+ *                       replace   torch.argmax(model(**sample).logits, dim=2) against the labels, and the loss / the
+ *                                 log-probability of given sequences, without the logits
+ *                                 markushgrapher/core/trainers/curriculumTrainer.py:654-672
  *   mg_create / mg_load_tensor / mg_finalize
  *                       replace   MarkushgrapherForConditionalGeneration.from_pretrained(...).to(device)
  *                                 /root/reference/markushgrapher/core/common/begin.py:128-133
@@ -98,6 +102,23 @@ int mg_encode(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_
  * decoder_attention_mask may be NULL.  Requires a preceding mg_encode on the same workspace. */
 int mg_decoder_forward(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* decoder_input_ids,
                        const uint8_t* decoder_attention_mask, int B, int T, float* logits);
+
+/* Scoring given target tokens: mg_decoder_forward up to the final norm, then the lm_head with the log-softmax, argmax and gather done in
+ * the kernel's epilogue (csrc/k_score.hip) - the [B][T][vocab] logits are never stored.  Replaces
+ *     logits = model(**sample).logits; torch.argmax(logits, dim=2) compared with the labels
+ *                                 markushgrapher/core/trainers/curriculumTrainer.py:654-672
+ * and cross_entropy(logits, labels) / the log-probability of a candidate sequence under the model.  Outputs, each [B][T] and nullable:
+ *   token_logprobs[b][t]  = log_softmax(logits[b][t])[targets[b][t]]; a negative target (stock's ignore_index) gives 0.0
+ *   argmax_ids[b][t]      = lowest index of the largest logit;  argmax_logprobs[b][t] = its log-probability
+ * targets may be NULL when token_logprobs is.  A target >= vocab is reported as MG_E_INPUT, like a bad token id.  Requires a preceding
+ * mg_encode on the same workspace and may be called several times after it (once per set of candidates).  SYNCHRONISES.  Deterministic;
+ * a position's results do not depend on B or T.
+ * WORKSPACE: mg_score_workspace_bytes = mg_workspace_bytes(B, L, 1, 0, T, M_e1) plus the kernel's partials (16 bytes per position and
+ * 1024 vocabulary columns); a workspace of that size also serves mg_encode / mg_decoder_forward of the same B, L, T. */
+int mg_score_workspace_bytes(const mg_model* m, int B, int L, int T, int M_e1, size_t* out_bytes);
+int mg_decoder_score(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* decoder_input_ids,
+                     const uint8_t* decoder_attention_mask, const int64_t* targets, int B, int T, float* token_logprobs,
+                     int64_t* argmax_ids, float* argmax_logprobs);
 
 /* generate(): encoder once, then KV-cached decode.  num_beams == 1: greedy (stock generation/utils.py:2783-2975);
  * num_beams > 1: beam search (utils.py:3208-3525, beams_to_keep = 2*num_beams, length_penalty, early_stopping 0/1).
@@ -584,6 +605,14 @@ int mgk_embed_norm_rows(void* stream, const int64_t* ids, const void* tok_emb, f
 int mgk_gemm_splitk(void* stream, const void* X_pk, const void* W_pk, float* P, int M, int N, int K, int ldp,
                     size_t slab_stride, int KS);
 int mgk_splitk_factor(int N, int K);
+/* lm_head of the teacher-forced path with the log-softmax / argmax / gather in the epilogue (csrc/k_score.hip; the [M][N] logits are never
+ * stored).  X_pk packed [M padded to 32][K], W_pk packed [N padded to 32][K] with zero pad rows, K % 64 == 0.  Per row m over the N real
+ * columns: lse = log-sum-exp; tok_lp = logit[targets[m]] - lse (target < 0: 0.0; >= N: 0.0, and the first int of scratch counts it);
+ * arg_id = lowest index of the largest logit; arg_lp = its logit - lse.  targets and every output are nullable; rows >= M are not written.
+ * scratch: mgk_score_scratch_bytes(M, N) bytes (16 per row and 1024-column slab of the vocabulary), MG_E_WORKSPACE if smaller. */
+size_t mgk_score_scratch_bytes(int M, int N);
+int mgk_score(void* stream, const void* X_pk, const void* W_pk, int M, int N, int K, const int64_t* targets, float* tok_lp, int64_t* arg_id,
+              float* arg_lp, float* lse, void* scratch, size_t scratch_bytes);
 /* A/B switch of the large-M GEMM kernel (0: 128x128 two-stage, 1: 256x128 three-stage, default) */
 int mgk_gemm_set_variant(int v);
 /* decode-step residual projection with the next RMSNorm folded in: h += X W^T (optionally scaled per row by the deferred

@@ -406,6 +406,19 @@ int mgk_lm_head_top(void* stream, const void* X_pk, const void* W_pk, float* P, 
     return MG_OK;
 }
 
+// lm_head with the log-softmax / argmax / gather epilogue (score_lm_head, k_score.hip): no logits; every output and `targets` nullable.
+// The first int of scratch counts the targets >= N of the call.
+size_t mgk_score_scratch_bytes(int M, int N) { return (M < 1 || N < 1) ? 0 : score_scratch_bytes(M, N); }
+int mgk_score(void* stream, const void* X_pk, const void* W_pk, int M, int N, int K, const int64_t* targets, float* tok_lp, int64_t* arg_id,
+              float* arg_lp, float* lse, void* scratch, size_t scratch_bytes) {
+    if (!X_pk || !W_pk || !scratch) return MG_E_ARG;
+    if (K < 64 || (K & 63) || M < 1 || N < 1) return MG_E_SHAPE;
+    if (scratch_bytes < score_scratch_bytes(M, N)) return MG_E_WORKSPACE;
+    const ScoreArgs a{(const uint16_t*)X_pk, (const uint16_t*)W_pk, M, N, K, targets, tok_lp, arg_id, arg_lp, lse, scratch};
+    score_lm_head(a, (mgStream_t)stream);
+    return MG_OK;
+}
+
 // mgk_lm_head_top as the decode step launches it: the deferred row scale of the final norm and up to four stop tokens (host array, -1 = unused);
 // ptop null: the plain projection (the unfused tail's launch)
 int mgk_lm_head_step(void* stream, const void* X_pk, const void* W_pk, float* P, int M, int N, int K, int ldp, const float* rs_part, int rs_nparts,

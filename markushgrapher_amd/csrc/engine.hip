@@ -1284,17 +1284,10 @@ int mg_encode(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_
     return check_launch("mg_encode");
 }
 
-int mg_decoder_forward(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* decoder_input_ids,
-                       const uint8_t* decoder_attention_mask, int B, int T, float* logits) {
-    entry_drain();
-    if (!m || !ws || !decoder_input_ids || !logits) return fail(MG_E_ARG, "mg_decoder_forward: null argument");
-    MG_ONE_CALL(m, "mg_decoder_forward");
-    if (m->st_ws != ws || m->st_B != B) return fail(MG_E_STATE, "mg_decoder_forward: run mg_encode on this workspace/batch first");
-    if (T < 1 || T > m->T_cap) return fail(MG_E_SHAPE, "mg_decoder_forward: T must be in [1, %d]", m->T_cap);
-    mgStream_t st = (mgStream_t)stream;
-    Ws w;
-    carve(m, (char*)ws, B, m->st_L, 1, 0, T, m->st_M, &w);
-    if (w.total > ws_bytes) return fail(MG_E_WORKSPACE, "mg_decoder_forward: workspace too small (%zu < %zu)", ws_bytes, w.total);
+// Teacher-forced decoder stack up to and including the final norm: leaves the B*T real positions, normalised and packed, in w.tf_xc
+// (the operand of the lm_head).  Shared by mg_decoder_forward (logits) and mg_decoder_score (fused log-probabilities).
+static void decoder_stack(mg_model* m, mgStream_t st, const Ws& w, const int64_t* decoder_input_ids, const uint8_t* decoder_attention_mask,
+                          int B, int T) {
     const int d = m->d, H = m->H, inner = m->inner;
     const int T_cap = round_up(T, 64), MT = B * T_cap, S = m->st_S, S_cap = m->st_Scap, M = B * S_cap;
     const int M64 = m->st_M > 0 ? round_up(m->st_M, 64) : 0, Sx_cap = S_cap + M64;
@@ -1342,7 +1335,21 @@ int mg_decoder_forward(mg_model* m, void* stream, void* ws, size_t ws_bytes, con
     // final norm, d_model^-0.5 (tied head, stock:1554-1555), lm_head on the B*T real positions only
     rmsnorm_pack_rows(w.tf_hidden, m->at<float>(m->dec_ln), w.tf_xc, w.tf_rowmap, MT, d, m->c.layer_norm_epsilon,
                       m->tied ? 1.0f / sqrtf((float)d) : 1.0f, st);
-    GemmArgs lg = gemm_args(w.tf_xc, m->at<uint16_t>(m->lm_head), B * T, m->V, d);
+}
+
+int mg_decoder_forward(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* decoder_input_ids,
+                       const uint8_t* decoder_attention_mask, int B, int T, float* logits) {
+    entry_drain();
+    if (!m || !ws || !decoder_input_ids || !logits) return fail(MG_E_ARG, "mg_decoder_forward: null argument");
+    MG_ONE_CALL(m, "mg_decoder_forward");
+    if (m->st_ws != ws || m->st_B != B) return fail(MG_E_STATE, "mg_decoder_forward: run mg_encode on this workspace/batch first");
+    if (T < 1 || T > m->T_cap) return fail(MG_E_SHAPE, "mg_decoder_forward: T must be in [1, %d]", m->T_cap);
+    mgStream_t st = (mgStream_t)stream;
+    Ws w;
+    carve(m, (char*)ws, B, m->st_L, 1, 0, T, m->st_M, &w);
+    if (w.total > ws_bytes) return fail(MG_E_WORKSPACE, "mg_decoder_forward: workspace too small (%zu < %zu)", ws_bytes, w.total);
+    decoder_stack(m, st, w, decoder_input_ids, decoder_attention_mask, B, T);
+    GemmArgs lg = gemm_args(w.tf_xc, m->at<uint16_t>(m->lm_head), B * T, m->V, m->d);
     lg.out_f32 = logits; lg.ldo = m->V;
     gemm(lg, EPI_F32_STORE, st);
     // out-of-range token ids (encoder or decoder side) were replaced by id 0 and counted: report them, as the
@@ -1353,6 +1360,47 @@ int mg_decoder_forward(mg_model* m, void* stream, void* ws, size_t ws_bytes, con
     const int rc = check_launch("mg_decoder_forward");
     if (rc != MG_OK) return rc;
     if (bad_ids != 0) return fail(MG_E_INPUT, "mg_decoder_forward: %d token ids outside [0, vocab)", bad_ids);
+    return MG_OK;
+}
+
+// the score kernel's scratch sits behind the teacher-forced layout: mg_workspace_bytes is untouched
+static size_t score_ws_total(const mg_model* m, const Ws& w, int B, int T) { return align_up(w.total + score_scratch_bytes(B * T, m->V), 256); }
+
+int mg_score_workspace_bytes(const mg_model* m, int B, int L, int T, int M_e1, size_t* out_bytes) {
+    if (!m || !out_bytes || B < 1 || L < 1 || T < 1 || M_e1 < 0) return fail(MG_E_ARG, "mg_score_workspace_bytes: bad argument");
+    Ws w;
+    if (M_e1 == 0) M_e1 = m->e1_M;
+    carve(m, nullptr, B, L, 1, 0, T, M_e1, &w);
+    *out_bytes = score_ws_total(m, w, B, T);
+    return MG_OK;
+}
+
+int mg_decoder_score(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* decoder_input_ids,
+                     const uint8_t* decoder_attention_mask, const int64_t* targets, int B, int T, float* token_logprobs,
+                     int64_t* argmax_ids, float* argmax_logprobs) {
+    entry_drain();
+    if (!m || !ws || !decoder_input_ids) return fail(MG_E_ARG, "mg_decoder_score: null argument");
+    if (!targets && token_logprobs) return fail(MG_E_ARG, "mg_decoder_score: token_logprobs needs targets");
+    MG_ONE_CALL(m, "mg_decoder_score");
+    if (m->st_ws != ws || m->st_B != B) return fail(MG_E_STATE, "mg_decoder_score: run mg_encode on this workspace/batch first");
+    if (T < 1 || T > m->T_cap) return fail(MG_E_SHAPE, "mg_decoder_score: T must be in [1, %d]", m->T_cap);
+    mgStream_t st = (mgStream_t)stream;
+    Ws w;
+    carve(m, (char*)ws, B, m->st_L, 1, 0, T, m->st_M, &w);
+    const size_t total = score_ws_total(m, w, B, T);
+    if (total > ws_bytes) return fail(MG_E_WORKSPACE, "mg_decoder_score: workspace too small (%zu < %zu): size it with mg_score_workspace_bytes", ws_bytes, total);
+    decoder_stack(m, st, w, decoder_input_ids, decoder_attention_mask, B, T);
+    char* scratch = (char*)ws + align_up(w.total, 256);
+    const ScoreArgs sa{w.tf_xc, m->at<uint16_t>(m->lm_head), B * T, m->V, m->d, targets, token_logprobs, argmax_ids, argmax_logprobs, nullptr, scratch};
+    score_lm_head(sa, st);
+    int bad_ids = 0, bad_targets = 0;
+    mg_memcpy_async(&bad_ids, w.counters + 3, sizeof(int), st);
+    mg_memcpy_async(&bad_targets, scratch, sizeof(int), st);
+    mg_stream_sync(st);
+    const int rc = check_launch("mg_decoder_score");
+    if (rc != MG_OK) return rc;
+    if (bad_ids != 0) return fail(MG_E_INPUT, "mg_decoder_score: %d token ids outside [0, vocab)", bad_ids);
+    if (bad_targets != 0) return fail(MG_E_INPUT, "mg_decoder_score: %d targets outside [ignored (< 0), vocab)", bad_targets);
     return MG_OK;
 }
 

@@ -120,6 +120,25 @@ struct TopOut {
 };
 void gemm_rows_splitk(const uint16_t* X, const uint16_t* W, float* P, int M, int N, int K, int ldp, size_t slab_stride, int KS,
                       const RowScale& rs, mgStream_t stream, const TopOut* top = nullptr);
+// lm_head of the teacher-forced path with the log-softmax / argmax / gather done in the epilogue (k_score.hip): the [M][N] logits are never
+// stored.  X packed [M padded to 32][K], W packed [N padded to 32][K] with zero pad rows, K % 64 == 0.  Per row m:
+//   lse = log-sum-exp over the N real columns;  tok_lp = logit[targets[m]] - lse (target < 0: 0.0; >= N: 0.0 and counted in the error
+//   word);  arg_id = lowest index of the largest logit;  arg_lp = its logit - lse.
+// Every output and `targets` are nullable.  scratch: score_scratch_bytes(M, N) bytes (16 per row and 1024-column slab); its first int
+// is the error word (targets >= N of this launch), cleared by the launcher.  Deterministic; a row's results do not depend on M.
+struct ScoreArgs {
+    const uint16_t* X;
+    const uint16_t* W;
+    int M, N, K;
+    const int64_t* targets;   // [M]
+    float* tok_lp;            // [M]
+    int64_t* arg_id;          // [M]
+    float* arg_lp;            // [M]
+    float* lse;               // [M]
+    void* scratch;
+};
+size_t score_scratch_bytes(int M, int N);
+void score_lm_head(const ScoreArgs& a, mgStream_t stream);
 // Residual projection of the decode step with the NEXT sub-layer's RMSNorm folded in (no separate norm launch):
 //   h[m][n] += sum_k X[m][k] W[n][k];   x_pk = pack(bf16(h * gain * gscale))  (un-normalised);
 //   part[m*(N/8) + n/8] = sum over the block's 8 features of h^2  (consumers turn them into r(m), see RowScale).

@@ -143,6 +143,9 @@ class Engine:
                                 C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.mg_decoder_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                          C.c_int, C.c_int, C.c_void_p]
+        L.mg_score_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+        L.mg_decoder_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mg_generate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
                                   C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]
@@ -371,6 +374,61 @@ class Engine:
         self._chk(self.lib.mg_decoder_forward(self.model, self.mem.stream(), self.mem.ptr(ws), nb, self.mem.ptr(dec),
                                               self.mem.ptr(dm) if dm is not None else None, B, T, self.mem.ptr(logits)))
         return logits, enc_out, enc_mask
+
+    def _score_workspace(self, B, L, T, M_e1):
+        """The context's workspace grown to mg_score_workspace_bytes (the teacher-forced layout plus the score kernel's partials).  Called
+        BEFORE the encode of a scoring call: a workspace that moved after mg_encode has lost the encoder state."""
+        need = C.c_size_t()
+        self._chk(self.lib.mg_score_workspace_bytes(self.model, B, L, T, M_e1, C.byref(need)))
+        if need.value > self._ws_bytes:
+            self._ws = None
+            self._ws = self.mem.empty((need.value,), np.uint8)
+            self._ws_bytes = need.value
+        return self._ws, self._ws_bytes
+
+    def _score_sets(self, enc_args, e1, sets):
+        """ONE mg_encode, then one mg_decoder_score per (decoder_input_ids, targets, decoder_attention_mask or None) of `sets`, each [B, T]
+        -> [(token_logprobs, argmax_ids, argmax_logprobs)]"""
+        sets = [(self.mem.asarray(d, np.int64), self.mem.asarray(t, np.int64), None if m is None else self.mem.asarray(m, np.uint8))
+                for d, t, m in sets]
+        B, T = (int(v) for v in sets[0][1].shape)
+        for d, t, m in sets:
+            if len(t.shape) != 2 or any(tuple(x.shape) != (B, T) for x in (d, t, m) if x is not None):
+                raise ValueError(f"decoder_input_ids, targets and decoder_attention_mask must all be [{B}, {T}] per candidate")
+        if int(enc_args[0].shape[0]) != B:
+            raise ValueError(f"targets are for {B} images, the encoder inputs for {int(enc_args[0].shape[0])}")
+        L, M_e1 = int(enc_args[0].shape[1]), 0 if e1 is None else int(e1.shape[1])
+        ws, nb = self._score_workspace(B, L, T, M_e1)          # (before the encode; Engine.encode's own sizing never shrinks it)
+        self.encode(*enc_args, T=T, want_out=False, e1=e1)
+        outs = []
+        for d, t, m in sets:
+            tok, arg, alp = self.mem.empty((B, T), np.float32), self.mem.empty((B, T), np.int64), self.mem.empty((B, T), np.float32)
+            self._chk(self.lib.mg_decoder_score(self.model, self.mem.stream(), self.mem.ptr(ws), nb, self.mem.ptr(d),
+                                                self.mem.ptr(m) if m is not None else None, self.mem.ptr(t), B, T, self.mem.ptr(tok),
+                                                self.mem.ptr(arg), self.mem.ptr(alp)))
+            outs.append((tok, arg, alp))
+        return outs
+
+    def score(self, input_ids, bbox, attention_mask, pixel_values, decoder_input_ids, targets, decoder_attention_mask=None, e1=None):
+        """Log-probabilities of given target tokens under the teacher-forced decoder (mg_decoder_score): the lm_head's log-softmax, argmax
+        and gather run in the kernel's epilogue, the [B, T, vocab] logits are never stored.  targets [B, T] int64, a negative target is
+        ignored (0.0).  -> token_logprobs [B, T] f32, argmax_ids [B, T] i64, argmax_logprobs [B, T] f32."""
+        return self._score_sets((input_ids, bbox, attention_mask, pixel_values), e1, [(decoder_input_ids, targets, decoder_attention_mask)])[0]
+
+    def score_candidates(self, input_ids, bbox, attention_mask, pixel_values, decoder_input_ids, candidates, decoder_attention_mask=None,
+                         e1=None):
+        """C candidate target sequences per image (an n-best list, samples, another tool's outputs): candidates [B, C, T] int64 with
+        decoder_input_ids [B, C, T] (and decoder_attention_mask [B, C, T] or None).  ONE mg_encode, then C mg_decoder_score calls on its
+        state.  -> token_logprobs, argmax_ids, argmax_logprobs, each [B, C, T]; candidate c equals score() of it alone, bit for bit."""
+        if len(candidates.shape) != 3 or tuple(decoder_input_ids.shape) != tuple(candidates.shape):
+            raise ValueError("candidates and decoder_input_ids must both be [B, C, T]")
+        dm = decoder_attention_mask
+        outs = self._score_sets((input_ids, bbox, attention_mask, pixel_values), e1,
+                                [(decoder_input_ids[:, c], candidates[:, c], None if dm is None else dm[:, c]) for c in range(int(candidates.shape[1]))])
+        if isinstance(outs[0][0], np.ndarray):
+            return tuple(np.stack([o[k] for o in outs], 1) for k in range(3))
+        import torch
+        return tuple(torch.stack([o[k] for o in outs], 1) for k in range(3))
 
     def debug_decode_capture(self, capture_steps=0, rows=0, forced_ids=None):
         """Parity-test instrumentation (include/mgrapher.h mg_debug_decode_capture): returns the device buffer

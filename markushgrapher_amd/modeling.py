@@ -86,6 +86,24 @@ class Seq2SeqLMOutput:
 
 
 @dataclass
+class ScoreOutput:
+    """score(): log-probabilities of given target sequences, computed on the device without the [.., vocab] logits.
+      token_logprobs     [B, T] or [B, C, T]: log_softmax(logits)[label]; 0.0 where the label is -100
+      sequence_logprobs  [B] or [B, C]: the sum of a sequence's token_logprobs over its non-ignored positions
+      loss               mean negative log-probability over the call's non-ignored positions (= forward(labels=...).loss)
+      argmax_ids         [B, T] or [B, C, T]: the model's own prediction at every position (ties: the lowest id)
+      argmax_logprobs    its log-probability"""
+    token_logprobs: torch.Tensor
+    sequence_logprobs: torch.Tensor
+    loss: torch.Tensor
+    argmax_ids: torch.Tensor
+    argmax_logprobs: torch.Tensor
+
+    def __getitem__(self, k):
+        return getattr(self, k)
+
+
+@dataclass
 class GenerateOutput:
     """generate(return_dict_in_generate=True): the fields of stock GenerateEncoderDecoderOutput / GenerateBeamEncoderDecoderOutput that
     this path fills, plus `token_scores`.
@@ -407,6 +425,36 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
             loss = nn.functional.cross_entropy(logits.view(-1, logits.size(-1)), labels.to(logits.device).view(-1),
                                                ignore_index=-100)
         return Seq2SeqLMOutput(loss=loss, logits=logits, encoder_last_hidden_state=enc, encoder_attention_mask=mask)
+
+    @torch.no_grad()
+    def score(self, input_ids, bbox, pixel_values, attention_mask=None, labels=None, decoder_input_ids=None, e1=None):
+        """Log-probability of given target sequences under the model, and the model's own prediction at every position - what the
+        reference's evaluation (core/trainers/curriculumTrainer.py:654-672: argmax of the logits against the labels), a loss, or the
+        re-ranking of candidates (an n-best list, samples, another OCSR tool's outputs) need - without the [B, T, vocab] logits:
+        Engine.score runs the lm_head with the log-softmax, argmax and gather in its epilogue.
+        labels [B, T], or [B, C, T] for C candidates per image (one encoder pass, C decoder passes); -100 marks ignored positions, exactly
+        as in forward()'s loss; decoder_input_ids default to _shift_right(labels).  -> ScoreOutput.  forward() is unchanged."""
+        if labels is None:
+            raise ValueError("score() needs labels")
+        self._check_e1(e1)
+        eng = self._eng()
+        if decoder_input_ids is None:
+            decoder_input_ids = self._shift_right(labels)
+        if tuple(decoder_input_ids.shape) != tuple(labels.shape):
+            raise ValueError("decoder_input_ids and labels must have the same shape")
+        if labels.dim() == 3:
+            tok, arg, alp = eng.score_candidates(input_ids, bbox, attention_mask, pixel_values, decoder_input_ids, labels, e1=e1)
+        elif labels.dim() == 2:
+            tok, arg, alp = eng.score(input_ids, bbox, attention_mask, pixel_values, decoder_input_ids, labels, e1=e1)
+        else:
+            raise ValueError(f"labels must be [B, T] or [B, C, T], got {tuple(labels.shape)}")
+        live = labels.to(tok.device) != -100
+        n = live.sum()
+        # (ignored positions hold 0.0: the plain sum is the masked sum; float64: the mean over B * T terms of one call)
+        loss = (-(tok.double().sum()) / n.clamp(min=1).double()).float()
+        if int(n) == 0:
+            loss = loss * float("nan")                  # cross_entropy's mean over no position
+        return ScoreOutput(token_logprobs=tok, sequence_logprobs=tok.sum(-1), loss=loss, argmax_ids=arg, argmax_logprobs=alp)
 
     def _default_mask(self, input_ids, attention_mask):
         if attention_mask is not None:
