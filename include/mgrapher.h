@@ -368,7 +368,7 @@ int mgk_pack_weight(void* stream, const void* src, int src_is_bf16, int N, int K
 int mgk_rmsnorm_pack(void* stream, const float* h, const float* gain, void* x_pk, float* out_f32, int M, int d,
                      float eps, float scale);
 int mgk_im2col_pack(void* stream, const float* pix, void* x_pk, int B, int C, int I, int ps);
-/* TEST / A-B SWITCHES (mgk_set_rows_split, mgk_set_resid_f16, mgk_gemm_set_variant, mgk_set_rows_mt, mgk_set_attention_qt, mgk_set_pp_parts): PROCESS-WIDE, for the parity tests and tools/.
+/* TEST / A-B SWITCHES (mgk_set_rows_split, mgk_set_resid_f16, mgk_gemm_set_variant, mgk_set_rows_mt, mgk_set_attention_qt, mgk_set_pp_parts, mgk_set_pp_groups): PROCESS-WIDE, for the parity tests and tools/.
  * Each selects among kernels whose results are bit-identical (that is what the tests that flip them check), so a call that races
  * with a flip still returns the right bits; they are nevertheless meant to be set while no call is running, and the product
  * (markushgrapher_amd/) never touches them.
@@ -390,6 +390,10 @@ int mgk_set_attention_qt(int qt);
 /* persistent ping-pong GEMM: the row tiles of one problem over several launches - 0 (default) never (problems with more tiles per workgroup
  * than the kernel's table holds go to the two-stage kernel: measured equally fast), 1 when needed, 2 .. 8 always that many (same bits) */
 int mgk_set_pp_parts(int mode);
+/* persistent ping-pong GEMM: at most that many workgroups per launch - 0 (default) no cap (one per CU), n > 0: min(tiles, CUs, n), rounded down
+ * to a multiple of 8 from 8 on as ever; < 0: back to MG_PP_GROUPS or the default.  The kernel takes its tile schedule from its grid, so a small
+ * cap makes every workgroup walk several tiles of a small problem (same bits) */
+int mgk_set_pp_groups(int cap);
 /* mgk_gemm_resid with the scratch of the K-slab form: kpart [16][M padded to 32][N] fp32, ticket [N / 32] i32 zero-initialised;
  * wide_tiles as ResidArgs (8 in the decode steps) */
 int mgk_gemm_resid_mt(void* stream, const void* X_pk, const void* W_pk, float* h, const float* gain, float gscale, void* x_pk,
@@ -413,6 +417,38 @@ int mgk_gemm_row_tiles(void* stream, int epi, const void* X_pk, const void* W_pk
                        const uint8_t* row_mask, int* list_scratch);
 int mgk_gemm_heads(void* stream, int mode, const void* X_pk, const void* W_pk, int M, int N, int K, void* p0, void* p1,
                    void* p2, int f0, int f1, int f2, int H, int S_in, int S_cap, const int* row_map, int pos);
+/* The tiled large-M GEMM (mode 0 of the entries above) with everything its call sites in the engines set, on operands the caller makes (test
+ * entry).  mgk_gemm_desc = GemmArgs: X packed [M padded to 32][K], W packed [N padded to 32][K]; by epilogue
+ *   0 / 1 (fp32 store + bias / accumulate): out_f32 [M][ldo], ldo >= N;
+ *   2 / 3 (packed relu / packed): out_pk packed [M][N], N % 16 == 0, rows scaled by the deferred RMSNorm scale rs_*;
+ *   5 (EPI_RESID_NORM): out_f32 = the tiled h (mgk_gemm_norm), N % 32 == 0; gain -> out_pk = pack(bf16(h * gain)); part [M][ldo] partial sums of
+ *     h^2 (ldo >= N / 64 rounded up); M % 32 == 0 when any of gain / out_pk / part is given;
+ *   4 (per head): N = 1 .. 3 regions of H * 64 columns, region i to head_ptr[i] in head_fmt[i] = 0 none (pointer may be null), 1 packed rows,
+ *     2 packed transposed ([B][H][S_cap] tokens, token s of image m / S_in at s + s_off: s_off + S_in <= S_cap, S_in, S_cap, s_off multiples
+ *     of 32), 3 natural [B][H][S_cap][64] at row row_map[m] (null: m % S_in; < 0: dropped; s_off must be 0); rows scaled by rs_*.
+ * rs_part [M][rs_nparts] (null: no scale; epilogues 2, 3, 4 only), rs_nparts a multiple of 4.
+ * row_mask [M] + list_scratch [M / 32 + 1] (M % 32 == 0, row_mask 16-byte aligned): the row-tile list is built from the mask as in
+ * mgk_gemm_row_tiles (a mask without an attended position gives the list {0}).  list_scratch alone: the caller's own list - [0] the count,
+ * then that many ascending tile ids < M / 32 - the only way to an empty one.  The 128 x 128 and 256 x 128 kernels (variants 0 / 1, M < 320,
+ * N < 256) have no list support and compute every row.
+ * Errors before any device work: MG_E_ARG a missing pointer, MG_E_SHAPE a size rule above, MG_E_UNSUPPORTED any other epilogue or format
+ * (the bias / GELU epilogues: mgk_gemm; the decode-step formats: mgk_gemm_heads_step) and a row scale on an epilogue that applies none. */
+typedef struct mgk_gemm_desc {
+    const void* X;
+    const void* W;
+    int M, N, K;
+    float* out_f32; int ldo;
+    const float* bias;
+    void* out_pk;
+    const float* gain;
+    float* part;
+    const float* rs_part; int rs_nparts; float rs_inv_d, rs_eps;
+    void* head_ptr[3]; int head_fmt[3];
+    int H, S_in, S_cap, s_off;
+    const int* row_map;
+    const uint8_t* row_mask; int* list_scratch;
+} mgk_gemm_desc;
+int mgk_gemm_ex(void* stream, const mgk_gemm_desc* d, int epi);
 /* mode 0 (encoder): tab1/tabh/tabv are the RAW bucket tables [32][H]; bk1[257] / bkhv[201] the bucket ids of integer
  * distances -128..128 / -100..100; bidx_scratch [B][Sk_cap/32][Sk_cap][32] u16 receives the per-pair bucket indices.
  * mode 1 (decoder self): tab1 = [tab1_len][H] by distance; mode 2 (cross): no bias. */

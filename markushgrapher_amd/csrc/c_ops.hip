@@ -579,6 +579,53 @@ int mgk_gemm_resid_mt(void* stream, const void* X_pk, const void* W_pk, float* h
 int mgk_set_rows_mt(int on) { gemm_rows_set_mt(on); return MG_OK; }
 int mgk_set_attention_qt(int qt) { attention_set_qt(qt); return MG_OK; }
 int mgk_set_pp_parts(int mode) { gemm_pp_set_parts(mode); return MG_OK; }
+int mgk_set_pp_groups(int cap) { gemm_pp_set_groups(cap); return MG_OK; }
+
+// The tiled gemm() with everything its call sites set (test entry; include/mgrapher.h).  Every check comes before any device work.
+int mgk_gemm_ex(void* stream, const mgk_gemm_desc* d, int epi) {
+    if (!d || !d->X || !d->W) return MG_E_ARG;
+    if (d->M < 1 || d->N < 1 || d->K < 64 || (d->K & 63)) return MG_E_SHAPE;
+    if (epi != EPI_F32_STORE && epi != EPI_F32_RESID && epi != EPI_PK_RELU && epi != EPI_PK && epi != EPI_HEADS && epi != EPI_RESID_NORM)
+        return MG_E_UNSUPPORTED;
+    const bool scaled = epi == EPI_PK_RELU || epi == EPI_PK || epi == EPI_HEADS;
+    if (d->rs_part && !scaled) return MG_E_UNSUPPORTED;
+    if (d->rs_part && (d->rs_nparts < 4 || (d->rs_nparts & 3))) return MG_E_SHAPE;
+    if ((d->row_mask && !d->list_scratch) || ((uintptr_t)d->row_mask & 15)) return MG_E_ARG;
+    if (d->list_scratch && (d->M & 31)) return MG_E_SHAPE;
+    GemmArgs a{};
+    a.X = (const uint16_t*)d->X; a.W = (const uint16_t*)d->W; a.M = d->M; a.N = d->N; a.K = d->K;
+    a.rs = RowScale{d->rs_part, d->rs_nparts, d->rs_inv_d, d->rs_eps};
+    if (epi == EPI_F32_STORE || epi == EPI_F32_RESID) {
+        if (!d->out_f32) return MG_E_ARG;
+        if (d->ldo < d->N) return MG_E_SHAPE;
+        a.out_f32 = d->out_f32; a.ldo = d->ldo; a.bias = d->bias;
+    } else if (epi == EPI_PK_RELU || epi == EPI_PK) {
+        if (!d->out_pk) return MG_E_ARG;
+        if (d->N & 15) return MG_E_SHAPE;
+        a.out_pk = (uint16_t*)d->out_pk;
+    } else if (epi == EPI_RESID_NORM) {
+        if (!d->out_f32 || (d->gain && !d->out_pk)) return MG_E_ARG;
+        if ((d->N & 31) || ((d->M & 31) && (d->gain || d->out_pk || d->part)) || (d->part && d->ldo < (d->N + 63) / 64)) return MG_E_SHAPE;
+        a.out_f32 = d->out_f32; a.gain = d->gain; a.out_pk = (uint16_t*)d->out_pk; a.part = d->part; a.ldo = d->ldo;
+    } else {
+        if (d->H < 1 || (d->N % (d->H * 64)) || d->N > 3 * d->H * 64 || d->S_in < 1 || d->S_cap < 1) return MG_E_SHAPE;
+        if (d->s_off < 0 || (d->s_off & 31) || d->s_off + d->S_in > d->S_cap) return MG_E_SHAPE;
+        for (int i = 0; i < 3; ++i) {
+            const int f = d->head_fmt[i];
+            if (f != HF_NONE && f != HF_PK_ROWS && f != HF_PK_T && f != HF_NATURAL) return MG_E_UNSUPPORTED;
+            if (i < d->N / (d->H * 64) && f != HF_NONE && !d->head_ptr[i]) return MG_E_ARG;
+            if ((f == HF_PK_ROWS || f == HF_PK_T) && ((d->S_cap & 31) || (d->S_in & 31))) return MG_E_SHAPE;
+            if (f == HF_NATURAL && d->s_off) return MG_E_SHAPE;
+            a.heads.ptr[i] = (uint16_t*)d->head_ptr[i]; a.heads.fmt[i] = f;
+        }
+        a.heads.inner = d->H * 64; a.heads.H = d->H; a.heads.S_in = d->S_in; a.heads.S_cap = d->S_cap; a.heads.s_off = d->s_off;
+        a.heads.row_map = d->row_map;
+    }
+    if (d->row_mask) row_tile_list(d->row_mask, d->M, d->list_scratch + 1, d->list_scratch, (mgStream_t)stream);
+    if (d->list_scratch) { a.row_tiles = d->list_scratch + 1; a.n_row_tiles = d->list_scratch; }      // (row_mask null: the caller's own list)
+    gemm(a, epi, (mgStream_t)stream);
+    return MG_OK;
+}
 
 #ifdef MG_TOOLS
 int mgk_gemm_resid_trace(void* stream, const void* X_pk, const void* W_pk, float* h, const float* gain, void* x_pk, float* part, int N,

@@ -315,6 +315,11 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs a) {
 static Switch g_pp_parts{"MG_PP_PARTS", 0};      // (the variable: A/B runs)
 void gemm_pp_set_parts(int mode) { if (mode < 0) g_pp_parts.reset(); else g_pp_parts.set(mode); }
 
+// workgroups per launch at most: 0 no cap (one per CU).  The kernel takes its schedule from gridDim.x: with a small cap every workgroup walks several
+// tiles of a small problem (tests, A/B runs; same bits)
+static Switch g_pp_groups{"MG_PP_GROUPS", 0};      // (the variable: A/B runs)
+void gemm_pp_set_groups(int cap) { if (cap < 0) g_pp_groups.reset(); else g_pp_groups.set(cap); }
+
 template <int EPI, int TI>
 static bool launch_pp(const GemmArgs& a_in, mgStream_t stream) {
     GemmArgs a = a_in;
@@ -331,6 +336,7 @@ static bool launch_pp(const GemmArgs& a_in, mgStream_t stream) {
     ncu = 8;
 #endif
     int G = nblk < ncu ? nblk : ncu;
+    if (const int cap = g_pp_groups.get(); cap > 0 && cap < G) G = cap;      // (MG_PP_GROUPS; 0: as before)
     if (G >= 8) G &= ~7;
     if ((a.K & 127) != 0 || (EPI == EPI_RESID_NORM && a.N > GP_GAIN_MAX)) return false;   // (K/16 a multiple of the ring)
     // more tiles per workgroup than the kernel's tile table holds (balanced blocks are up to 30 % more; the FFN input projection of a 160-image

@@ -93,6 +93,7 @@ void gemm(const GemmArgs& a, int epi, mgStream_t stream);
 bool gemm_has_gelu_epilogue(int M, int N);     // EPI_PK_GELU exists in the 320x256 / 256x256 tile kernels only
 bool gemm_pp(const GemmArgs& a, int epi, int ti, mgStream_t stream);   // k_gemm_pp.hip: persistent ping-pong tile kernel (ti = 4, 5); false = shape not supported
 void gemm_pp_set_parts(int mode); // ping-pong kernel: row tiles of one problem over several launches - 0 (default) never, 1 when its tile table is too small, 2 .. 8 always that many (tests; same bits)
+void gemm_pp_set_groups(int cap); // ping-pong kernel: at most that many workgroups per launch - 0 (default) no cap, < 0 back to MG_PP_GROUPS or the default (tests, A/B runs; same bits)
 void gemm_set_variant(int v);   // 0: 128x128 kernel only; 1: + 256x128 three-stage; 2: + 256x256; 4: + 320x256 wherever it fits; 3 (default): by shape
 
 // small-M (decode step) GEMM: M <= 32*MT rows of live sequences, weights streamed once.
