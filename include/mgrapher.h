@@ -500,6 +500,51 @@ int mgk_embed_assemble(void* stream, void* meta_ws, const int64_t* input_ids, co
                        const void* y_emb, int B, int L, int P, int d, int n_side, int M2, int V, int S_cap,
                        float* hidden, double* cx, double* cy, uint8_t* mask, int* xrow, int* xlen, int* err);
 size_t mgk_embed_meta_bytes(int B, int S_cap);
+/* The stage in front of the first encoder GEMM and behind the last one, in every form mg_encode runs it (test entries; kernels of
+ * csrc/k_embed.hip, k_attn.hip, k_pack.hip, k_xattn.hip and the output copies of engine.hip).  Every entry checks its arguments before any
+ * device work: MG_E_ARG a missing pointer, MG_E_SHAPE a size rule.
+ * mgk_embed_desc = EmbedArgs (csrc/mg_kernels.h) + meta_ws (mgk_embed_meta_bytes(B, S_cap) bytes): hidden [B][S_cap][d] fp32 row-major, or
+ * the tiled layout of mgk_gemm_norm's h_tiled when hidden_tiled (S_cap % 32 == 0); cx / cy [B][S_cap] f64; mask [B][S_cap]; xrow [B][S_cap] =
+ * x_row0 + rank among the attended positions, or -1; xlen [B] = x_row0 + attended positions; trim_padding = 1 with an attention mask: the
+ * layout [text Lb | patches | moved text padding], Lb = last attended text token + 1; text_len [B] nullable receives Lb (L otherwise).
+ * Rules: S_cap >= L + P, P == n_side * n_side, d % 4 == 0, x_row0 >= 0. */
+typedef struct mgk_embed_desc {
+    const int64_t* input_ids; const float* bbox; const uint8_t* attention_mask; const float* patch_emb;
+    const void* tok_emb; const void* x_emb; const void* y_emb;
+    int B, L, P, d, n_side, M2, V, S_cap;
+    float* hidden; int hidden_tiled;
+    double* cx; double* cy; uint8_t* mask; int* xrow; int* xlen; int x_row0;
+    int trim_padding; int* text_len; int* err;
+    void* meta_ws;
+} mgk_embed_desc;
+int mgk_embed_assemble_ex(void* stream, const mgk_embed_desc* e);
+/* bias_index: out [B][S_cap/32][S_cap][32] u16 = byte address 4 * (32 * vertical bucket + horizontal bucket) of every (query, key) pair, keys
+ * of a tile in accumulator order (entry half*16 + r <-> key (r%4) + 8*(r/4) + 4*half), 4 * 1024 for keys >= Sk or with kmask 0 (kmask
+ * [B][S_cap] nullable); bkhv [201] buckets of the distances -100 .. 100; bk1 is not read.  S_cap % 64 == 0, Sk <= S_cap. */
+int mgk_bias_index(void* stream, void* out, const double* cx, const double* cy, const uint8_t* kmask, const int* bk1, const int* bkhv, int B,
+                   int Sk, int S_cap);
+/* attn_lists: kst [B][1 + S_cap/64] = count, ascending ids of the 64-key stages with an attended key < Sk ({1, 0} when there is none);
+ * qbv [B][ceil(S_cap/128)] = 1 for a 128-query block with one.  S_cap % 64 == 0, Sk <= S_cap. */
+int mgk_attn_lists(void* stream, const uint8_t* kmask, int B, int Sk, int S_cap, int* kst, uint8_t* qbv);
+/* row_tile_list: list = ascending ids of the 32-row tiles of kmask [rows] with a non-zero byte, *count their number ({0}, 1 when there is
+ * none); entries behind the count are not written.  rows % 32 == 0, kmask 16-byte aligned. */
+int mgk_row_tile_list(void* stream, const uint8_t* kmask, int rows, int* list, int* count);
+/* pack_e1: e1 [B][M][d] fp32 -> e1_pk packed bf16 [B * M_pad][d] (rows >= M zero), row_map [B * M_pad] = j < M ? j : -1 and, when xmask is
+ * given, xmask [B][M_pad + S_cap] = [1 x M | 0 | enc_mask [B][S_cap]].  M_pad % 32 == 0, M_pad >= M, d % 16 == 0, S_cap % 64 == 0. */
+int mgk_pack_e1(void* stream, const float* e1, int B, int M, int M_pad, int d, void* e1_pk, int* row_map, const uint8_t* enc_mask, int S_cap,
+                uint8_t* xmask);
+/* The two output copies of mg_encode: enc_out [B][S][d] / enc_mask [B][S] in the order [text L | patches S - L] from the workspace rows
+ * enc_f32 [B][S_cap][d] / mask [B][S_cap]; text_len [B] (nullable) = text lengths Lb of the layout [text Lb | patches | text padding L - Lb].
+ * Either output may be null.  L <= S <= S_cap, d % 4 == 0. */
+int mgk_enc_copy_out(void* stream, const float* enc_f32, const uint8_t* mask, float* enc_out, uint8_t* enc_mask, int B, int S, int S_cap, int d,
+                     int L, const int* text_len);
+/* embed_rows: h [rows][d] fp32 = tok_emb [V][d] bf16 rows of ids (an id outside [0, V) is counted in *err and reads row 0); x_pk (nullable):
+ * the same rows into columns [x_col0, x_col0 + d) of a packed bf16 buffer x_ld wide.  d % 4 == 0, x_ld % 16 == 0, x_col0 % 4 == 0. */
+int mgk_embed_rows(void* stream, const int64_t* ids, const void* tok_emb, float* h, int rows, int d, int V, int* err, void* x_pk, int x_ld,
+                   int x_col0);
+/* rmsnorm_pack_rows: packed row dst_row[m] of x_pk = bf16(RMSNorm(h[m]) * gain * scale); dst_row[m] < 0: row m is skipped; dst_row null: m.
+ * d % 16 == 0. */
+int mgk_rmsnorm_pack_rows(void* stream, const float* h, const float* gain, void* x_pk, const int* dst_row, int M, int d, float eps, float scale);
 int mgk_greedy_select(void* stream, const float* logits, int rows, int V, int ldl, int eos, int pad, int min_len,
                       int64_t* next_ids, int64_t* out_ids, int max_len, int pos, int* unfinished, int* n_unfinished,
                       float* top2);

@@ -837,6 +837,72 @@ int mgk_embed_norm_rows(void* stream, const int64_t* ids, const void* tok_emb, f
     return MG_OK;
 }
 
+// ---- the encoder's input assembly, index tables and output copies in every form mg_encode runs them (test entries; include/mgrapher.h) ----
+// The launchers check nothing: what each assumes about its arguments is refused here, before any device work.
+int mgk_embed_assemble_ex(void* stream, const mgk_embed_desc* e) {
+    if (!e || !e->meta_ws || !e->input_ids || !e->bbox || !e->patch_emb || !e->tok_emb || !e->x_emb || !e->y_emb) return MG_E_ARG;
+    if (!e->hidden || !e->cx || !e->cy || !e->mask || !e->xrow || !e->xlen || !e->err) return MG_E_ARG;
+    if (e->B < 1 || e->L < 1 || e->n_side < 1 || e->n_side > 256 || e->M2 < 1 || e->V < 1 || e->d < 4) return MG_E_SHAPE;
+    if (e->P != e->n_side * e->n_side || e->S_cap < e->L + e->P || (e->d & 3) || e->x_row0 < 0) return MG_E_SHAPE;
+    if (e->hidden_tiled && (e->S_cap & 31)) return MG_E_SHAPE;
+    EmbedArgs a{};
+    a.input_ids = e->input_ids; a.bbox = e->bbox; a.attn_mask = e->attention_mask; a.patch_emb = e->patch_emb;
+    a.tok_emb = (const uint16_t*)e->tok_emb; a.x_emb = (const uint16_t*)e->x_emb; a.y_emb = (const uint16_t*)e->y_emb;
+    a.B = e->B; a.L = e->L; a.P = e->P; a.d = e->d; a.n_side = e->n_side; a.M2 = e->M2; a.V = e->V; a.S_cap = e->S_cap;
+    a.hidden = e->hidden; a.hidden_tiled = e->hidden_tiled ? 1 : 0; a.cx = e->cx; a.cy = e->cy; a.mask = e->mask; a.xrow = e->xrow;
+    a.xlen = e->xlen; a.x_row0 = e->x_row0; a.trim_padding = e->trim_padding ? 1 : 0; a.text_len = e->text_len; a.err = e->err;
+    embed_assemble(a, e->meta_ws, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_bias_index(void* stream, void* out, const double* cx, const double* cy, const uint8_t* kmask, const int* bk1, const int* bkhv, int B,
+                   int Sk, int S_cap) {
+    if (!out || !cx || !cy || !bkhv) return MG_E_ARG;                    // (bk1 belongs to the launcher's signature; the kernel does not read it)
+    if (B < 1 || S_cap < 64 || (S_cap & 63) || Sk < 0 || Sk > S_cap) return MG_E_SHAPE;
+    bias_index((uint16_t*)out, cx, cy, kmask, bk1, bkhv, B, Sk, S_cap, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_attn_lists(void* stream, const uint8_t* kmask, int B, int Sk, int S_cap, int* kst, uint8_t* qbv) {
+    if (!kmask || !kst || !qbv) return MG_E_ARG;
+    if (B < 1 || S_cap < 64 || (S_cap & 63) || Sk < 0 || Sk > S_cap) return MG_E_SHAPE;
+    attn_lists(kmask, B, Sk, S_cap, kst, qbv, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_row_tile_list(void* stream, const uint8_t* kmask, int rows, int* list, int* count) {
+    if (!kmask || !list || !count || ((uintptr_t)kmask & 15)) return MG_E_ARG;
+    if (rows < 32 || (rows & 31)) return MG_E_SHAPE;
+    row_tile_list(kmask, rows, list, count, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_pack_e1(void* stream, const float* e1, int B, int M, int M_pad, int d, void* e1_pk, int* row_map, const uint8_t* enc_mask, int S_cap,
+                uint8_t* xmask) {
+    if (!e1 || !e1_pk || !row_map || (xmask && !enc_mask)) return MG_E_ARG;
+    if (B < 1 || M < 1 || M_pad < M || (M_pad & 31) || d < 16 || (d & 15)) return MG_E_SHAPE;
+    if (S_cap < 0 || (S_cap & 63) || (xmask && S_cap < 64)) return MG_E_SHAPE;
+    pack_e1(e1, B, M, M_pad, d, (uint16_t*)e1_pk, row_map, enc_mask, S_cap, xmask, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_enc_copy_out(void* stream, const float* enc_f32, const uint8_t* mask, float* enc_out, uint8_t* enc_mask, int B, int S, int S_cap, int d,
+                     int L, const int* text_len) {
+    if ((!enc_out && !enc_mask) || (enc_out && !enc_f32) || (enc_mask && !mask)) return MG_E_ARG;
+    if (B < 1 || L < 0 || S < 1 || L > S || S > S_cap || d < 4 || (d & 3)) return MG_E_SHAPE;
+    enc_copy_out(enc_f32, mask, enc_out, enc_mask, B, S, S_cap, d, L, text_len, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_embed_rows(void* stream, const int64_t* ids, const void* tok_emb, float* h, int rows, int d, int V, int* err, void* x_pk, int x_ld,
+                   int x_col0) {
+    if (!ids || !tok_emb || !h || !err) return MG_E_ARG;
+    if (rows < 1 || d < 4 || (d & 3) || V < 1) return MG_E_SHAPE;
+    if (x_pk && ((x_ld & 15) || x_col0 < 0 || (x_col0 & 3) || x_col0 + d > x_ld)) return MG_E_SHAPE;
+    embed_rows(ids, (const uint16_t*)tok_emb, h, rows, d, V, err, (mgStream_t)stream, (uint16_t*)x_pk, x_ld, x_col0);
+    return MG_OK;
+}
+int mgk_rmsnorm_pack_rows(void* stream, const float* h, const float* gain, void* x_pk, const int* dst_row, int M, int d, float eps, float scale) {
+    if (!h || !gain || !x_pk) return MG_E_ARG;
+    if (M < 1 || d < 16 || (d & 15)) return MG_E_SHAPE;
+    rmsnorm_pack_rows(h, gain, (uint16_t*)x_pk, dst_row, M, d, eps, scale, (mgStream_t)stream);
+    return MG_OK;
+}
+
 size_t mg_preprocess_scratch_bytes(int B, int Hs, int Ws, int out_size) {
     if (B < 1 || Hs < 1 || Ws < 1 || out_size < 1) return 0;
     return preprocess_scratch_bytes(B, Hs, Ws, out_size);

@@ -626,6 +626,14 @@ void accumulate_cross_profile(mg_model* m, double keys) {
 
 }  // namespace
 
+namespace mg {
+void enc_copy_out(const float* enc_f32, const uint8_t* mask, float* enc_out, uint8_t* enc_mask, int B, int S, int S_cap, int d, int L,
+                  const int* text_len, mgStream_t stream) {
+    if (enc_out) MG_LAUNCH(copy_rows_kernel, dim3(1024), dim3(256), 0, stream, enc_f32, enc_out, B, S, S_cap, d, L, text_len);
+    if (enc_mask) MG_LAUNCH(copy_bytes_rows_kernel, dim3(64), dim3(256), 0, stream, mask, enc_mask, B, S, S_cap, L, text_len);
+}
+}  // namespace mg
+
 // Everything one decode step needs besides the model: the buffers of the live rows, the cross K/V streams they read and the
 // selection state.  Two users: mg_generate (one batch, all rows at the same position) and mg_generate_stream (continuous
 // decoding: `slots.pos` non-null, every row at its own position on its own image, K/V streams in a pool).
@@ -1275,8 +1283,7 @@ int mg_encode(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_
     }
     rmsnorm_pack_tiled(w.hidden, m->at<float>(m->enc_ln), w.enc_pk, w.enc_f32, M, d, m->c.layer_norm_epsilon, st);
     const int* tl = m->trim_padding ? w.text_len : nullptr;
-    if (enc_out) MG_LAUNCH(copy_rows_kernel, dim3(1024), dim3(256), 0, st, (const float*)w.enc_f32, enc_out, B, S, S_cap, d, L, tl);
-    if (enc_mask) MG_LAUNCH(copy_bytes_rows_kernel, dim3(64), dim3(256), 0, st, (const uint8_t*)w.mask, enc_mask, B, S, S_cap, L, tl);
+    enc_copy_out(w.enc_f32, w.mask, enc_out, enc_mask, B, S, S_cap, d, L, tl, st);
     // e1 tokens (OCSR vision branch, precomputed by the caller): fused with the VTL states by concatenation in front of the
     // decoder (ref: README.md:212-215) - here: packed next to them for the cross-K/V projections, never normalised or mixed
     if (e1) pack_e1(e1, B, M_e1, round_up(M_e1, 64), d, w.e1_pk, w.e1_map, w.mask, S_cap, w.xmask, st);

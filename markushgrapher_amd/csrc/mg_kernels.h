@@ -378,6 +378,11 @@ void xattn_stream_beams(const XAttnArgs& a, mgStream_t stream);
 void xattn_pack_weights(const float* wkv_f32, uint16_t* wk, uint16_t* wv, int H, int d, mgStream_t stream);
 // rows of a packed [rows][d] bf16 operand -> natural rows dst[b][row_map[r]][d] (row_map < 0: dropped)
 void enc_rows(const uint16_t* src_pk, const int* row_map, uint16_t* dst, int B, int rows_per_image, int cap, int d, mgStream_t stream);
+// the encoder's outputs in the documented [text L | patches P] order (engine.hip): enc_out [B][S][d] fp32 from the workspace rows enc_f32
+// [B][S_cap][d], enc_mask [B][S] from mask [B][S_cap]; text_len (nullable) = the per-image text lengths of the trimmed layout
+// [text Lb | patches P | text padding L - Lb].  Either output may be null (not written)
+void enc_copy_out(const float* enc_f32, const uint8_t* mask, float* enc_out, uint8_t* enc_mask, int B, int S, int S_cap, int d, int L,
+                  const int* text_len, mgStream_t stream);
 // rows [len[b], next multiple of 16) of dst[b] zeroed (the stream reads whole stages of 16 keys)
 void enc_pad_rows(uint16_t* dst, const int* len, int B, int cap, int d, mgStream_t stream);
 
