@@ -206,6 +206,53 @@ int mg_generate_sampled(mg_model* m, void* stream, void* ws, size_t ws_bytes, co
                         const uint8_t* attention_mask, const float* pixel_values, const float* e1, int M_e1, int B, int L, int max_length,
                         int min_length, int64_t* out_ids, int* out_cols_host, float* step_top2, const mg_sample_opts* opts);
 
+/* Decoder prompt (stock generate(decoder_input_ids=...)): fix the beginning of every answer and let the model write the rest.  One entry
+ * for the three batch decode modes: mg_generate_scored's arguments (greedy, beam search; opts nullable), or a sampled call (samp non-NULL:
+ * mg_generate_sampled's semantics, num_beams must be 1, opts / length_penalty / early_stopping / out_scores are not used), plus the prompt.
+ * prompt == NULL is exactly the unprompted call.
+ *   Image b has the prompt ids[b][0 .. len_host[b]); ids[b][0] is the token fed at step 0 (stock puts decoder_start_token_id there).  It
+ * serves all rows of the image: its num_beams beams or its samp->num_return samples.  Every row starts at column 0 and the call keeps ONE
+ * step counter.  While the column a row writes is below its prompt length the selection kernel writes the prompt's token there, not its
+ * own choice; afterwards the row decodes freely.  The forced steps are ordinary decode steps: they fill the self-attention cache through
+ * the same projection and attention launches, so positions, relative bias and cache layout are those of the unprompted call, and the
+ * forcing happens inside the selection kernels, under the captured decode step (mg_set_decode_graph 0 / 1 / 2 all take it).  A forced column
+ *   - never finishes a row, even when the forced token is EOS (stock tests generated tokens only);
+ *   - consumes no random draw (the draws are counter-based on (seed, stream id, column): free columns draw what they would draw anyway);
+ *   - leaves token_scores at 0.0 - the log-probability of a given prefix is what mg_decoder_score returns;
+ *   - keeps the row live for the attention launches.
+ * min_length keeps its meaning: EOS is suppressed while the column is below min_length, prompt columns included (stock's
+ * MinLengthLogitsProcessor counts the whole sequence).  Outputs include the prompt columns; *out_cols_host counts them.
+ *   Beam search follows stock _beam_search with decoder_prompt_len = len_host[b], per image: the K rows start holding the prompt with scores
+ * [0, -1e9, ...]; a forced column appends the token to every beam (beam index = identity, running scores and the finished set untouched,
+ * log-probability history 0); from the image's first free column on the finished-score divisor is (cur_len + 1 - len)^length_penalty and the
+ * early-stop heuristic's best hypothetical length cur_len - len.  beam_indices hold the image's beam-0 flat row in forced columns
+ * (non-negative, so compute_transition_scores keeps working), token_scores 0.0.
+ *   Two properties follow.  (1) Self-prefix identity: if the prompt is a prefix of what the same call emits unprompted (greedy; sampled with
+ * the same seed and stream ids), ids, length and the free columns of token_scores are bit-identical to the unprompted call; a prompt of
+ * [start] alone IS the unprompted call, in all three modes.  (2) Row b of a ragged batch equals the call on image b alone with its prompt,
+ * under the conditions of the project's call-size independence (cross-attention form pinned).
+ *   Checks: ids / len_host non-NULL, ld >= 1, 1 <= len_host[b] <= ld and len_host[b] < max_length (MG_E_ARG); a prompt while
+ * mg_debug_decode_capture's forced ids are set: MG_E_UNSUPPORTED (its logits capture alone keeps working); a prompt id outside [0, vocab) is
+ * replaced by id 0, never indexes the embedding table, and the call returns MG_E_INPUT, as for encoder ids.
+ *   WORKSPACE: mg_prompted_workspace_bytes = the unprompted call's size (mg_workspace_bytes with rows_per_image = num_beams, or
+ * mg_sampled_workspace_bytes with rows_per_image = num_return when sampled != 0) plus the [B] lengths, which are validated on the host
+ * and uploaded behind the unprompted layout.  ids stay where the caller put them: keep them (and the workspace) in place between calls
+ * and a later call of the same shape replays the captured step (pointers and ld are part of its key, the lengths are device data).
+ *   NOT built: the queue forms (mg_generate_stream*) and the OCR stage under a prompt; a PREFILL of the prompt - one teacher-forced pass
+ * that writes the self-attention cache of all prompt positions would replace len - 1 decode steps, and would give up property (1): its
+ * large-M projections sum in another order than the decode step's. */
+typedef struct mg_decoder_prompt {
+    const int64_t* ids;       /* [B][ld] device */
+    const int32_t* len_host;  /* [B] host */
+    int ld;
+} mg_decoder_prompt;
+int mg_prompted_workspace_bytes(const mg_model* m, int B, int L, int rows_per_image, int max_length, int M_e1, int sampled, size_t* out_bytes);
+int mg_generate_prompted(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
+                         const uint8_t* attention_mask, const float* pixel_values, const float* e1, int M_e1, int B, int L, int num_beams,
+                         int max_length, int min_length, float length_penalty, int early_stopping, int64_t* out_ids, int* out_cols_host,
+                         float* out_scores, float* step_top2, const mg_gen_opts* opts, const mg_sample_opts* samp,
+                         const mg_decoder_prompt* prompt);
+
 /* Continuous greedy decoding of N images - what the reference's evaluation loop does one image at a time with
  * model.generate(**encoding, num_beams=1, max_length=512) until EOS (/root/reference/markushgrapher/utils/ocsr/utils_evaluation.py:140,
  * 269-285), for a whole queue of images: `slots` decode rows work through the queue, a row that ends (EOS / max_length) frees its
@@ -598,6 +645,18 @@ int mgk_select_ex(void* stream, const mgk_select_desc* s);
 int mgk_sample_select_queue(void* stream, const float* logits, int rows, int V, int ldl, int eos, int pad, int min_len, float temperature,
                             int top_k, float top_p, uint64_t seed, const uint64_t* stream_ids, int64_t* next_ids, int64_t* out_ids, int max_len,
                             int pos, int* unfinished, int* n_unfinished, float* token_scores, int ts_ld, const mgk_slot_table* slots);
+/* The selection step under a decoder prompt (mg_generate_prompted; DecPrompt in csrc/mg_kernels.h), batch forms only (a slot table with a
+ * prompt: MG_E_ARG).  prompt_ids [owners][prompt_ld] i64 and prompt_len [owners] i32, both device; row r takes the prompt of owner
+ * r / group (group 0 / 1: its own); *bad (nullable) counts prompt ids outside [0, V), which are replaced by id 0.  While the column written
+ * is below the row's prompt length the row emits the prompt's token, scores 0.0, draws nothing and stays unfinished; the unfinished count
+ * and the step counters see it as a live row.  mgk_select_prompted = mgk_select_ex (fused or not); mgk_sample_select_prompted =
+ * mgk_sample_select with pos_dev / step_ctr as the engine's launch has them (nullable) - neither clears n_unfinished. */
+int mgk_select_prompted(void* stream, const mgk_select_desc* s, const int64_t* prompt_ids, const int* prompt_len, int prompt_ld, int group,
+                        int* bad);
+int mgk_sample_select_prompted(void* stream, const float* logits, int rows, int V, int ldl, int eos, int pad, int min_len, float temperature,
+                               int top_k, float top_p, uint64_t seed, const uint64_t* stream_ids, int64_t* next_ids, int64_t* out_ids, int max_len,
+                               int pos, const int* pos_dev, int* unfinished, int* n_unfinished, int* step_ctr, float* token_scores, int ts_ld,
+                               const int64_t* prompt_ids, const int* prompt_len, int prompt_ld, int group, int* bad);
 /* slot_refill (csrc/k_decode.hip) after a selection: idle slots take the next ready sequences of the queue.  1 <= rows <= 256, nsamp >= 1,
  * pool_cap >= 1. */
 int mgk_slot_refill(void* stream, const mgk_slot_table* slots, int64_t* next_ids, int* unfinished, int rows);
@@ -783,6 +842,15 @@ int mgk_beam_slots_step(void* stream, void* state, int slots, int K, int max_len
                         int* img, int* pool, int* bpool, int* live, int* assign, int64_t* next_ids, int* anc, int T_cap, int pool_cap,
                         int64_t* out_ids, int* out_len, float* out_scores, int* ctr, int end_first, int num_return, int* beam_indices,
                         float* token_scores);
+/* init / step of the batch form under a decoder prompt (mg_generate_prompted): prompt_ids [B][prompt_ld] i64, prompt_len [B] i32 (device; one
+ * prompt per image, 1 <= len <= prompt_ld, len < max_len).  init: the K rows of image b hold its prompt (ids outside [0, V) -> 0, counted
+ * in *bad, nullable).  step: an image whose cur_len is below its prompt length appends the forced token to every beam (beam_idx = identity);
+ * otherwise stock's step with decoder_prompt_len = its length.  div_table [max_len + 1] is required in both the by-value and the tdev form. */
+int mgk_beam_init_prompted(void* stream, void* state, int B, int K, int max_len, int pad, int eos, int start, int64_t* next_ids, int* anc,
+                           int T_cap, int* counters, const int64_t* prompt_ids, const int* prompt_len, int prompt_ld, int V, int* bad);
+int mgk_beam_step_prompted(void* stream, void* state, const float* logits, int ldl, int V, int B, int K, int max_len, int cur_len, const int* tdev,
+                           const float* div_table, int eos, int min_len, float length_penalty, int early_stopping, int64_t* next_ids,
+                           int* beam_idx, int* counters, const int64_t* prompt_ids, const int* prompt_len, int prompt_ld);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
  * ChemicalOCR stage ("next" row f-1).  Replaces, for the OCR pass that produces the cells the main model

@@ -334,9 +334,10 @@ static SlotTable slot_table(const mgk_slot_table* t) {
     for (int k = 0; k < 4; ++k) s.stop[k] = t->stop[k];
     return s;
 }
-int mgk_select_ex(void* stream, const mgk_select_desc* s) {
+static int select_impl(void* stream, const mgk_select_desc* s, const DecPrompt& prompt) {
     if (!s || !s->next_ids || !s->out_ids || !s->unfinished) return MG_E_ARG;
     const bool queue = s->slots.pos != nullptr;
+    if (prompt.ids && (queue || !prompt.len || prompt.ld < 1 || prompt.group < 0)) return MG_E_ARG;      // (a prompt belongs to the batch forms)
     if (s->fused && queue) return MG_E_ARG;                              // (the fused tail has no queue form)
     if (queue ? (!s->slots.img || !s->slots.ctr || !s->slots.out_len) : !s->n_unfinished) return MG_E_ARG;
     if (s->n_eos_more < 0 || s->n_eos_more > 3) return MG_E_ARG;
@@ -361,7 +362,34 @@ int mgk_select_ex(void* stream, const mgk_select_desc* s) {
     a.ptop = (const float4*)s->ptop; a.stopv = s->stopv; a.ntiles = s->ntiles; a.tok_emb = (const uint16_t*)s->tok_emb; a.h = s->h;
     a.gain = s->gain; a.x_pk = (uint16_t*)s->x_pk; a.x2_pk = (uint16_t*)s->x2_pk; a.x2_ld = s->x2_ld; a.x2_col0 = s->x2_col0; a.d = s->d;
     a.eps = s->eps; a.token_scores = s->token_scores; a.ts_ld = s->ts_ld;
+    a.prompt = prompt;
     if (s->fused) greedy_select_fused(a, (mgStream_t)stream); else greedy_select(a, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_select_ex(void* stream, const mgk_select_desc* s) { return select_impl(stream, s, DecPrompt{}); }
+// mgk_select_ex under a decoder prompt (DecPrompt, mg_kernels.h): batch forms only
+int mgk_select_prompted(void* stream, const mgk_select_desc* s, const int64_t* prompt_ids, const int* prompt_len, int prompt_ld, int group,
+                        int* bad) {
+    if (!prompt_ids) return MG_E_ARG;
+    return select_impl(stream, s, DecPrompt{prompt_ids, prompt_len, prompt_ld, group, bad});
+}
+// mgk_sample_select under a decoder prompt, with the step bookkeeping of the engine's launch (pos_dev / step_ctr nullable)
+int mgk_sample_select_prompted(void* stream, const float* logits, int rows, int V, int ldl, int eos, int pad, int min_len, float temperature,
+                               int top_k, float top_p, uint64_t seed, const uint64_t* stream_ids, int64_t* next_ids, int64_t* out_ids, int max_len,
+                               int pos, const int* pos_dev, int* unfinished, int* n_unfinished, int* step_ctr, float* token_scores, int ts_ld,
+                               const int64_t* prompt_ids, const int* prompt_len, int prompt_ld, int group, int* bad) {
+    if (!logits || !next_ids || !out_ids || !unfinished || !n_unfinished || rows < 1 || ldl < V || (ldl & 3)) return MG_E_ARG;
+    if (!(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f)) return MG_E_ARG;
+    if (!prompt_ids || !prompt_len || prompt_ld < 1 || group < 0) return MG_E_ARG;
+    if (rows > 256 || max_len < 1 || (token_scores && ts_ld < max_len - 1)) return MG_E_SHAPE;
+    if (!sample_select_supported(V)) return MG_E_UNSUPPORTED;
+    SampleArgs a{};
+    a.logits = logits; a.rows = rows; a.V = V; a.ldl = ldl; a.eos = eos; a.pad = pad; a.min_len = min_len;
+    a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.seed = seed; a.stream_ids = stream_ids;
+    a.next_ids = next_ids; a.out_ids = out_ids; a.max_len = max_len; a.pos = pos; a.pos_dev = pos_dev; a.unfinished = unfinished;
+    a.n_unfinished = n_unfinished; a.step_ctr = step_ctr; a.token_scores = token_scores; a.ts_ld = ts_ld;
+    a.prompt = DecPrompt{prompt_ids, prompt_len, prompt_ld, group, bad};
+    sample_select(a, (mgStream_t)stream);      // (n_unfinished is not cleared: the caller sets it, the step_ctr path clears it)
     return MG_OK;
 }
 int mgk_sample_select_queue(void* stream, const float* logits, int rows, int V, int ldl, int eos, int pad, int min_len, float temperature,
@@ -475,6 +503,26 @@ int mgk_beam_step(void* stream, void* state, const float* logits, int ldl, int V
     const BeamSlots bs{slot_pos, slot_live};
     beam_step(state, logits, ldl, V, B, K, max_len, cur_len, tdev, div_table, eos, min_len, length_penalty, early_stopping, next_ids, beam_idx,
               counters, (mgStream_t)stream, slot_pos ? &bs : nullptr);
+    return MG_OK;
+}
+// mgk_beam_init / mgk_beam_step (batch form) under a decoder prompt: prompt_ids [B][prompt_ld], prompt_len [B] device; div_table
+// [max_len + 1] is required (the per-image divisor index lives on the device)
+int mgk_beam_init_prompted(void* stream, void* state, int B, int K, int max_len, int pad, int eos, int start, int64_t* next_ids, int* anc,
+                           int T_cap, int* counters, const int64_t* prompt_ids, const int* prompt_len, int prompt_ld, int V, int* bad) {
+    if (!beam_geometry_ok(B, K, max_len) || T_cap < max_len - 1 || V < 2 * K) return MG_E_SHAPE;
+    if (!prompt_ids || !prompt_len || prompt_ld < 1) return MG_E_ARG;
+    const DecPrompt pr{prompt_ids, prompt_len, prompt_ld, 1, bad};
+    beam_init(state, B, K, max_len, pad, eos, start, next_ids, anc, T_cap, counters, (mgStream_t)stream, &pr, V);
+    return MG_OK;
+}
+int mgk_beam_step_prompted(void* stream, void* state, const float* logits, int ldl, int V, int B, int K, int max_len, int cur_len, const int* tdev,
+                           const float* div_table, int eos, int min_len, float length_penalty, int early_stopping, int64_t* next_ids,
+                           int* beam_idx, int* counters, const int64_t* prompt_ids, const int* prompt_len, int prompt_ld) {
+    if (!beam_geometry_ok(B, K, max_len) || V < 2 * K || ldl < V) return MG_E_SHAPE;
+    if (!div_table || !prompt_ids || !prompt_len || prompt_ld < 1) return MG_E_ARG;
+    const DecPrompt pr{prompt_ids, prompt_len, prompt_ld, 1, nullptr};
+    beam_step(state, logits, ldl, V, B, K, max_len, cur_len, tdev, div_table, eos, min_len, length_penalty, early_stopping, next_ids, beam_idx,
+              counters, (mgStream_t)stream, nullptr, &pr);
     return MG_OK;
 }
 int mgk_beam_reorder_anc(void* stream, int* anc, const int* beam_idx, int rows, int t_written, const int* tdev, const int* counters,

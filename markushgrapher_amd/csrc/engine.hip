@@ -64,8 +64,11 @@ struct BatchStepKey {        // mg_generate / mg_generate_sampled
     float temperature, top_p;
     uint64_t seed;
     const void* stream_ids;
+    // prompted calls (mg_generate_prompted): the selection launches hold the prompt's pointers (the lengths are device data: not part of the key)
+    const void *prompt_ids, *prompt_len;
+    int prompt_ld;
     MG_KEY_MEMBERS(BatchStepKey, ws, out_ids, step_top2, stream, B, L, K, max_length, min_length, early_stopping, M_e1, length_penalty,
-                   token_scores, num_return, top_k, temperature, top_p, seed, stream_ids)
+                   token_scores, num_return, top_k, temperature, top_p, seed, stream_ids, prompt_ids, prompt_len, prompt_ld)
 };
 struct QueueStepKey {        // mg_generate_stream*: greedy, sampled and beam queues
     const void *ws, *out_ids, *out_len, *stream;
@@ -119,6 +122,7 @@ struct mg_model {
     CapturedStep<QueueStepKey> stream_graph;        // continuous decoding (mg_generate_stream)
     void reset_step_graphs() { step_graph.reset(); stream_graph.reset(); }
     std::vector<float> beam_div_host;
+    std::vector<int32_t> prompt_len_host;           // mg_generate_prompted: the validated lengths, source of the call's upload
     int use_graph = 1;
     bool graph_active = false;
     // Greedy decoding with the weight-absorbed cross-attention (k_xattn.hip): a layer streams the encoder states once instead of its K and V.
@@ -209,11 +213,13 @@ __global__ __launch_bounds__(256) void build_table_kernel(const float* raw, cons
         out[i] = raw[bucket[i / H] * H + (i % H)];
 }
 
+// prompt (ids non-null): column 0 and the first fed token are the row's prompt[0] instead of the start token
 __global__ __launch_bounds__(256) void fill_ids_kernel(int64_t* next_ids, int64_t* out_ids, int* unfinished, int* counters, int rows,
-                                                  int max_len, int64_t start, int64_t pad) {
+                                                  int max_len, int64_t start, int64_t pad, DecPrompt prompt, int V) {
     const int r = blockIdx.x;
     for (int j = threadIdx.x; j < max_len; j += blockDim.x) out_ids[(size_t)r * max_len + j] = (j == 0) ? start : pad;
-    if (threadIdx.x == 0) {
+    if (threadIdx.x == 0) {         // (the thread that wrote column 0)
+        if (prompt_forced(prompt, r, 0, V, start)) out_ids[(size_t)r * max_len] = start;
         next_ids[r] = start;
         unfinished[r] = 1;
         if (r == 0) { counters[0] = rows; counters[1] = -1; counters[2] = 0; counters[5] = 0; counters[6] = 0; }   // [3] keeps the encoder's input-error count
@@ -658,6 +664,7 @@ struct DecodeCtx : DecodeBufs {
     float* token_scores;
     BeamOut nbest;
     const mg_sample_opts* samp;   // sampled call (mg_generate_sampled, mg_generate_stream_sampled): the selection is sample_select; rows of an image read its K/V through slots.pool
+    DecPrompt prompt;             // mg_generate_prompted (batch forms; ids null: none): greedy / sampled per row (group = samples per image), beam per image
 };
 
 // Decode step, 6 launches per layer: QKV -> self-attention -> [O residual | cross-Q] -> cross-attention ->
@@ -794,6 +801,7 @@ static void decode_step(mg_model* m, const DecodeCtx& c, int t, const int* tdev,
         g.step_ctr = stream ? nullptr : counters;      // the last workgroup to finish does the step bookkeeping (no step_end launch)
         g.slots = c.slots;
         g.token_scores = c.token_scores; g.ts_ld = max_length - 1;
+        g.prompt = c.prompt;
         if (c.samp) {
             SampleArgs sa{};
             sa.logits = c.logits; sa.rows = R; sa.V = m->V; sa.ldl = ldl; sa.eos = g.eos; sa.pad = g.pad; sa.min_len = min_length;
@@ -802,6 +810,7 @@ static void decode_step(mg_model* m, const DecodeCtx& c, int t, const int* tdev,
             sa.pos = g.pos; sa.pos_dev = tdev; sa.unfinished = c.unfinished; sa.n_unfinished = g.n_unfinished; sa.top2 = g.top2;
             sa.step_ctr = g.step_ctr; sa.token_scores = c.token_scores; sa.ts_ld = max_length - 1;
             sa.slots = c.slots;            // queue form: the row's column, output row and random stream come from the slot table
+            sa.prompt = c.prompt;
             sample_select(sa, st);
         } else if (fused_tail) {
             g.ptop = c.ptop; g.stopv = c.stopv; g.ntiles = ldl / 32;
@@ -825,7 +834,7 @@ static void decode_step(mg_model* m, const DecodeCtx& c, int t, const int* tdev,
                         c.out_scores, c.slots.ctr, true, st, &c.nbest);
     } else {
         beam_step(c.beam_state, c.logits, ldl, m->V, B, K, max_length, t + 1, tdev, c.beam_div, m->c.eos_token_id, min_length,
-                  length_penalty, early_stopping, c.next_ids, c.beam_idx, counters, st);
+                  length_penalty, early_stopping, c.next_ids, c.beam_idx, counters, st, nullptr, &c.prompt);
         beam_reorder_anc(c.anc, c.beam_idx, R, tdev ? max_length - 1 : t + 1, tdev, counters, st);
     }
     if (K > 1 && !stream) MG_LAUNCH(step_end_kernel, dim3(1), dim3(64), 0, st, counters, 0);
@@ -1421,6 +1430,8 @@ int mg_generate(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int6
 
 }  // extern "C"
 
+static size_t prompt_ws_bytes(int B) { return align_up((size_t)B * sizeof(int32_t), 256); }      // mg_generate_prompted: the lengths, behind the unprompted layout
+
 // owner[r] = r / group: the image whose encoder states row r of a sampled call reads
 __global__ void row_owner_kernel(int* owner, int rows, int group) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1433,7 +1444,8 @@ __global__ void row_owner_kernel(int* owner, int rows, int group) {
 static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
                          const uint8_t* attention_mask, const float* pixel_values, const float* e1, int M_e1, int B, int L, int num_beams,
                          int max_length, int min_length, float length_penalty, int early_stopping, int64_t* out_ids, int* out_cols_host,
-                         float* out_scores, float* step_top2, const mg_gen_opts* opts, const mg_sample_opts* samp, const char* who) {
+                         float* out_scores, float* step_top2, const mg_gen_opts* opts, const mg_sample_opts* samp, const char* who,
+                         const mg_decoder_prompt* prompt = nullptr) {
     entry_drain();
     if (!m || !out_ids || !out_cols_host) return fail(MG_E_ARG, "%s: null argument", who);
     std::unique_lock<std::recursive_mutex> call_lock(m->call_mu, std::try_to_lock);      // MG_ONE_CALL under the entry's own name
@@ -1458,6 +1470,19 @@ static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
     }
     int32_t* beam_indices = opts ? opts->beam_indices : nullptr;
     if (max_length < 2 || max_length > m->T_cap) return fail(MG_E_SHAPE, "%s: max_length must be in [2, %d]", who, m->T_cap);
+    if (prompt) {
+        if (!prompt->ids || !prompt->len_host || prompt->ld < 1) return fail(MG_E_ARG, "%s: decoder prompt needs ids, len_host and ld >= 1", who);
+        if (B < 1) return fail(MG_E_ARG, "%s: B must be >= 1", who);
+        if (m->dbg_forced)
+            return fail(MG_E_UNSUPPORTED, "%s: a decoder prompt and forced ids (mg_debug_decode_capture) are not supported together", who);
+        for (int b = 0; b < B; ++b) {
+            const int len = prompt->len_host[b];
+            if (len < 1 || len > prompt->ld)
+                return fail(MG_E_ARG, "%s: decoder prompt length of image %d (%d) must be in [1, ld = %d]", who, b, len, prompt->ld);
+            if (len >= max_length)
+                return fail(MG_E_ARG, "%s: decoder prompt length of image %d (%d) must be below max_length (%d)", who, b, len, max_length);
+        }
+    }
     if (num_beams < 1 || num_beams > 8) return fail(MG_E_UNSUPPORTED, "%s: num_beams must be in [1, 8]", who);
     // the decode-step projections keep all live rows of a workgroup's feature slice in registers: at most 8 row tiles
     if ((long)B * num_beams > 256)
@@ -1471,7 +1496,8 @@ static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
     if (!e1 && m->e1m) M_e1 = m->e1_M;            // attached OCSR branch: mg_encode evaluates it (same workspace layout as with precomputed tokens)
     if (samp) carve(m, (char*)ws, B, L, NS, max_length, 0, M_e1, &w, 1);
     else carve(m, (char*)ws, B, L, K, max_length, 0, M_e1, &w);
-    if (w.total > ws_bytes) return fail(MG_E_WORKSPACE, "%s: workspace too small (%zu < %zu)", who, ws_bytes, w.total);
+    const size_t ws_need = w.total + (prompt ? prompt_ws_bytes(B) : 0);      // the prompt lengths [B] follow the unprompted layout
+    if (ws_need > ws_bytes) return fail(MG_E_WORKSPACE, "%s: workspace too small (%zu < %zu)", who, ws_bytes, ws_need);
     if (m->phase_on) mg_event_record(m->phase_ev[0], st);
     int rc = mg_encode(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, e1, M_in, B, L, nullptr, nullptr);
     if (rc != MG_OK) return rc;
@@ -1485,10 +1511,18 @@ static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
     int* counters = w.counters;
     const int64_t start = m->c.decoder_start_token_id, pad = m->c.pad_token_id;
     if (m->use_graph == 1) st = m->fork.from(st);      // (a null stream cannot be captured)
+    DecPrompt dp{};
+    if (prompt) {      // the validated lengths go up from a vector of the context's (the call ends with a host synchronisation of st)
+        m->prompt_len_host.assign(prompt->len_host, prompt->len_host + B);
+        int* len_dev = (int*)((char*)ws + w.total);
+        mg_memcpy_async(len_dev, m->prompt_len_host.data(), (size_t)B * sizeof(int32_t), st);
+        dp.ids = prompt->ids; dp.len = len_dev; dp.ld = prompt->ld; dp.group = NS; dp.bad = counters + 3;
+    }
     if (K == 1) {
-        MG_LAUNCH(fill_ids_kernel, dim3(R), dim3(64), 0, st, db.next_ids, out_ids, db.unfinished, counters, R, max_length, start, pad);
+        MG_LAUNCH(fill_ids_kernel, dim3(R), dim3(64), 0, st, db.next_ids, out_ids, db.unfinished, counters, R, max_length, start, pad, dp, m->V);
     } else {
-        beam_init(db.beam_state, B, K, max_length, (int)pad, m->c.eos_token_id, (int)start, db.next_ids, db.anc, T_cap, counters, st);
+        beam_init(db.beam_state, B, K, max_length, (int)pad, m->c.eos_token_id, (int)start, db.next_ids, db.anc, T_cap, counters, st,
+                  prompt ? &dp : nullptr, m->V);
         upload_beam_div(m, db.beam_div, max_length, length_penalty, st);
     }
     int steps_done = 0;
@@ -1508,6 +1542,7 @@ static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
         mg_memset_async(token_scores, 0, (size_t)R * (max_length - 1) * sizeof(float), st);
     }
     dc.samp = samp;
+    dc.prompt = dp;
     if (samp && NS > 1) {              // (the ancestor table's buffer is free: a sampled call has no beams.  The live-row skip of the attention
                                        // launches is per ROW in both cross-attention forms, so the samples of an image finish independently)
         MG_LAUNCH(row_owner_kernel, dim3((R + 255) / 256), dim3(256), 0, st, db.anc, R, NS);
@@ -1529,6 +1564,7 @@ static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
         key.B = B; key.L = L; key.K = K; key.max_length = max_length; key.min_length = min_length; key.early_stopping = early_stopping;
         key.M_e1 = M_e1; key.length_penalty = length_penalty; key.token_scores = dc.token_scores; key.num_return = NS;
         if (samp) { key.top_k = samp->top_k; key.temperature = samp->temperature; key.top_p = samp->top_p; key.seed = samp->seed; key.stream_ids = samp->stream_ids; }
+        key.prompt_ids = dp.ids; key.prompt_len = dp.len; key.prompt_ld = dp.ld;
         graphed = m->step_graph.ensure(key, st, who, [&] { decode_step(0, counters + 2, false); });
     }
     m->graph_active = graphed;
@@ -1587,7 +1623,7 @@ static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
         m->phase_dec_ms += mg_event_elapsed_ms(m->phase_ev[1], m->phase_ev[2]);
         m->phase_n += 1;
     }
-    if (host_flag[3] != 0) return fail(MG_E_INPUT, "%s: %d token ids outside [0, vocab)", who, host_flag[3]);
+    if (host_flag[3] != 0) return fail(MG_E_INPUT, "%s: %d token ids outside [0, vocab)", who, host_flag[3]);      // (encoder ids and prompt ids)
     if (K == 1) *out_cols_host = 1 + (host_flag[1] >= 0 ? host_flag[1] + 1 : steps_done);
     else *out_cols_host = beam_cols;
     return MG_OK;
@@ -1609,6 +1645,30 @@ int mg_generate_sampled(mg_model* m, void* stream, void* ws, size_t ws_bytes, co
     if (!opts) return fail(MG_E_ARG, "mg_generate_sampled: null options");
     return generate_impl(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, e1, M_e1, B, L, 1, max_length, min_length, 1.0f,
                          0, out_ids, out_cols_host, nullptr, step_top2, nullptr, opts, "mg_generate_sampled");
+}
+
+int mg_prompted_workspace_bytes(const mg_model* m, int B, int L, int rows_per_image, int max_length, int M_e1, int sampled, size_t* out_bytes) {
+    if (!out_bytes || B < 1) return fail(MG_E_ARG, "mg_prompted_workspace_bytes: null argument or B < 1");
+    size_t base = 0;
+    const int rc = sampled ? mg_sampled_workspace_bytes(m, B, L, rows_per_image, max_length, M_e1, &base)
+                           : mg_workspace_bytes(m, B, L, rows_per_image, max_length, 0, M_e1, &base);
+    if (rc != MG_OK) return rc;
+    *out_bytes = base + prompt_ws_bytes(B);
+    return MG_OK;
+}
+
+int mg_generate_prompted(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
+                         const uint8_t* attention_mask, const float* pixel_values, const float* e1, int M_e1, int B, int L, int num_beams,
+                         int max_length, int min_length, float length_penalty, int early_stopping, int64_t* out_ids, int* out_cols_host,
+                         float* out_scores, float* step_top2, const mg_gen_opts* opts, const mg_sample_opts* samp,
+                         const mg_decoder_prompt* prompt) {
+    if (samp) {
+        if (num_beams != 1) return fail(MG_E_ARG, "mg_generate_prompted: a sampled call takes num_beams = 1 (got %d)", num_beams);
+        return generate_impl(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, e1, M_e1, B, L, 1, max_length, min_length, 1.0f,
+                             0, out_ids, out_cols_host, nullptr, step_top2, nullptr, samp, "mg_generate_prompted", prompt);
+    }
+    return generate_impl(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, e1, M_e1, B, L, num_beams, max_length, min_length,
+                         length_penalty, early_stopping, out_ids, out_cols_host, out_scores, step_top2, opts, nullptr, "mg_generate_prompted", prompt);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

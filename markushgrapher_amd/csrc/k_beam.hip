@@ -74,17 +74,28 @@ static BeamPtrs beam_ptrs(void* state, int B, int K, int max_len) {
 }
 
 // utils.py:3316-3351 initial values (fill value = pad_token_id or eos: pad id 0 is falsy -> EOS, utils.py:3319)
+// Decoder prompt (pr.ids non-null): the K rows of image b hold its prompt in columns [0, len[b]) of both sequence arrays, as stock starts
+// them (utils.py:3326-3327); the running histories of the forced columns hold the image's beam-0 row and log-probability 0.
 __global__ __launch_bounds__(256) void beam_init_kernel(BeamPtrs p, int B, int K, int max_len, int fill, int start, int64_t* next_ids,
-                                                   int* anc, int T_cap, int* counters) {
+                                                   int* anc, int T_cap, int* counters, DecPrompt pr, int V) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const int R = B * K;
+    const int plen = pr.ids ? pr.len[b] : 0;
     for (int i = tid; i < K * max_len; i += 256) {
-        const int64_t v = (i % max_len == 0) ? start : fill;
+        const int j = i % max_len;
+        int64_t v = (j == 0) ? start : fill;
+        if (j < plen) {
+            v = pr.ids[(size_t)b * pr.ld + j];
+            if (v < 0 || v >= (int64_t)V) {
+                if (i < max_len && pr.bad) atomicAdd(pr.bad, 1);      // once per (image, column)
+                v = 0;
+            }
+        }
         p.running_seq[(size_t)b * K * max_len + i] = v;
         p.sequences[(size_t)b * K * max_len + i] = v;
     }
     for (int i = tid; i < K * (max_len - 1); i += 256) {
-        p.run_idx[(size_t)b * K * (max_len - 1) + i] = -1;
+        p.run_idx[(size_t)b * K * (max_len - 1) + i] = (i % (max_len - 1)) < plen - 1 ? b * K : -1;
         p.beam_idx_out[(size_t)b * K * (max_len - 1) + i] = -1;
         p.run_lp[(size_t)b * K * (max_len - 1) + i] = 0.f;
         p.lp_out[(size_t)b * K * (max_len - 1) + i] = 0.f;
@@ -93,7 +104,12 @@ __global__ __launch_bounds__(256) void beam_init_kernel(BeamPtrs p, int B, int K
         p.running_scores[b * K + i] = i == 0 ? 0.f : -1.0e9f;
         p.beam_scores[b * K + i] = -1.0e9f;
         p.is_fin[b * K + i] = 0;
-        next_ids[b * K + i] = start;
+        int64_t first = start;
+        if (plen > 0) {
+            first = pr.ids[(size_t)b * pr.ld];
+            if (first < 0 || first >= (int64_t)V) first = 0;
+        }
+        next_ids[b * K + i] = first;
     }
     for (int i = tid; i < T_cap * K; i += 256) {   // identity ancestor table for this image's rows
         const int j = i / K, k = i - j * K;
@@ -105,9 +121,10 @@ __global__ __launch_bounds__(256) void beam_init_kernel(BeamPtrs p, int B, int K
     }
 }
 void beam_init(void* state, int B, int K, int max_len, int pad, int eos, int start, int64_t* next_ids, int* anc, int T_cap,
-               int* counters, mgStream_t stream) {
+               int* counters, mgStream_t stream, const DecPrompt* prompt, int V) {
     const BeamPtrs p = beam_ptrs(state, B, K, max_len);
-    MG_LAUNCH(beam_init_kernel, dim3(B), dim3(256), 0, stream, p, B, K, max_len, pad ? pad : eos, start, next_ids, anc, T_cap, counters);
+    const DecPrompt pr = prompt ? *prompt : DecPrompt{};
+    MG_LAUNCH(beam_init_kernel, dim3(B), dim3(256), 0, stream, p, B, K, max_len, pad ? pad : eos, start, next_ids, anc, T_cap, counters, pr, V);
 }
 
 MG_DEV bool cand_before(float v1, int i1, float v2, int i2) { return v1 > v2 || (v1 == v2 && i1 < i2); }
@@ -137,11 +154,13 @@ MG_DEV float block_sum16(float v, float* red, int tid) {
     return r;
 }
 __global__ __launch_bounds__(BT_THREADS) void beam_row_topk_kernel(BeamPtrs p, const float* logits, int ldl, int V, int K, int cur_len_arg,
-                                                              int eos, int min_len, const int* counters, const int* tdev, BeamSlots bs) {
+                                                              int eos, int min_len, const int* counters, const int* tdev, BeamSlots bs,
+                                                              DecPrompt pr) {
     // queue form (bs.pos): every image slot is at its own length, idle slots are skipped; batch form: one length, the batch's
     // continue flag
     if (bs.pos ? bs.live[blockIdx.x] == 0 : counters[0] == 0) return;
     const int cur_len = bs.pos ? bs.pos[blockIdx.x] + 1 : (tdev ? *tdev + 1 : cur_len_arg);
+    if (pr.ids && cur_len < pr.len[blockIdx.x / K]) return;      // a forced column of the image's prompt: nothing is ranked
     MG_DYN_SMEM(smem);
     float* red = (float*)smem;            // [16]
     float* selv = red + 16;               // [16]
@@ -229,8 +248,10 @@ __global__ __launch_bounds__(BT_THREADS) void beam_row_topk_kernel(BeamPtrs p, c
     }
 }
 // rank of every row candidate among the image's K*2K; ranks < 2K are the image's top-2K in order
-__global__ __launch_bounds__(128) void beam_merge_topk_kernel(BeamPtrs p, int K, const int* counters, BeamSlots bs) {
+__global__ __launch_bounds__(128) void beam_merge_topk_kernel(BeamPtrs p, int K, const int* counters, BeamSlots bs, int cur_len_arg,
+                                                         const int* tdev, DecPrompt pr) {
     if (bs.pos ? bs.live[blockIdx.x * K] == 0 : counters[0] == 0) return;
+    if (pr.ids && (tdev ? *tdev + 1 : cur_len_arg) < pr.len[blockIdx.x]) return;
     MG_DYN_SMEM(smem);
     const int b = blockIdx.x, tid = threadIdx.x, keep = 2 * K, n = K * keep;
     float* cv = (float*)smem;             // [128]
@@ -247,12 +268,25 @@ __global__ __launch_bounds__(128) void beam_merge_topk_kernel(BeamPtrs p, int K,
 // c.-g. bookkeeping for one image (K <= 8, 2K <= 16 candidates)
 __global__ __launch_bounds__(256) void beam_update_kernel(BeamPtrs p, int B, int K, int V, int max_len, int cur_len_arg, int eos,
                                                      float div_arg, const float* div_table, int early_stopping, int64_t* next_ids,
-                                                     int* beam_idx, const int* counters, const int* tdev, BeamSlots bs) {
+                                                     int* beam_idx, const int* counters, const int* tdev, BeamSlots bs, DecPrompt pr) {
     if (bs.pos ? bs.live[blockIdx.x * K] == 0 : counters[0] == 0) return;
     const int cur_len = bs.pos ? bs.pos[blockIdx.x * K] + 1 : (tdev ? *tdev + 1 : cur_len_arg);
-    // (cur_len + 1 - prompt_len)^length_penalty with prompt_len = 1: the divisor of the finished-beam score
-    // (utils.py:3182) and, after the increment of cur_len, of the early-stop heuristic (utils.py:3047-3052)
-    const float fin_div = div_table ? div_table[cur_len] : div_arg;
+    // Decoder prompt: stock's decoder_prompt_len of THIS image (1 without a prompt).  A forced column appends the prompt's token (in the
+    // sequence arrays since beam_init) to every beam: the beam index is the identity, running scores and the finished set stay as they
+    // are, and the image's loop condition says "continue" (it has not ranked anything yet).
+    const int plen = pr.ids ? pr.len[blockIdx.x] : 1;
+    if (cur_len < plen) {
+        const int b = blockIdx.x, tid = threadIdx.x;
+        if (tid < K) {
+            next_ids[b * K + tid] = p.running_seq[((size_t)b * K + tid) * max_len + cur_len];
+            beam_idx[b * K + tid] = b * K + tid;
+        }
+        if (tid == 0) { p.flags[b * 4 + 0] = 1; p.flags[b * 4 + 1] = 0; p.flags[b * 4 + 2] = 0; }
+        return;
+    }
+    // (cur_len + 1 - prompt_len)^length_penalty: the divisor of the finished-beam score (utils.py:3182) and, after the increment of
+    // cur_len, of the early-stop heuristic's best hypothetical length cur_len - prompt_len (utils.py:3047-3052).  div_table[c] = c^penalty
+    const float fin_div = div_table ? div_table[cur_len + 1 - plen] : div_arg;
     const float heur_div = fin_div;
     MG_DYN_SMEM(smem);
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -412,14 +446,17 @@ float beam_length_divisor(int cur_len, float length_penalty) { return (float)pow
 // filled on the host with beam_length_divisor so both forms use bit-identical values)
 void beam_step(void* state, const float* logits, int ldl, int V, int B, int K, int max_len, int cur_len, const int* tdev,
                const float* div_table, int eos, int min_len, float length_penalty, int early_stopping, int64_t* next_ids,
-               int* beam_idx, int* counters, mgStream_t stream, const BeamSlots* slots) {
+               int* beam_idx, int* counters, mgStream_t stream, const BeamSlots* slots, const DecPrompt* prompt) {
     const BeamPtrs p = beam_ptrs(state, B, K, max_len);
     const BeamSlots bs = slots ? *slots : BeamSlots{nullptr, nullptr};
-    MG_LAUNCH(beam_row_topk_kernel, dim3(B * K), dim3(BT_THREADS), 256, stream, p, logits, ldl, V, K, cur_len, eos, min_len, (const int*)counters, tdev, bs);
-    MG_LAUNCH(beam_merge_topk_kernel, dim3(B), dim3(128), 1024, stream, p, K, (const int*)counters, bs);
+    // a prompt belongs to the batch form and always takes its divisor from div_table (the prompt lengths live on the device)
+    const DecPrompt pr = (prompt && !bs.pos) ? *prompt : DecPrompt{};
+    MG_LAUNCH(beam_row_topk_kernel, dim3(B * K), dim3(BT_THREADS), 256, stream, p, logits, ldl, V, K, cur_len, eos, min_len, (const int*)counters, tdev, bs,
+              pr);
+    MG_LAUNCH(beam_merge_topk_kernel, dim3(B), dim3(128), 1024, stream, p, K, (const int*)counters, bs, cur_len, tdev, pr);
     const float div = beam_length_divisor(cur_len, length_penalty);
-    MG_LAUNCH(beam_update_kernel, dim3(B), dim3(256), 1024, stream, p, B, K, V, max_len, cur_len, eos, div, (tdev || bs.pos) ? div_table : nullptr,
-              early_stopping, next_ids, beam_idx, (const int*)counters, tdev, bs);
+    MG_LAUNCH(beam_update_kernel, dim3(B), dim3(256), 1024, stream, p, B, K, V, max_len, cur_len, eos, div,
+              (tdev || bs.pos || pr.ids) ? div_table : nullptr, early_stopping, next_ids, beam_idx, (const int*)counters, tdev, bs, pr);
     if (!bs.pos) MG_LAUNCH(beam_flags_kernel, dim3(1), dim3(64), 0, stream, p, B, early_stopping, counters);
 }
 

@@ -467,11 +467,13 @@ __global__ __launch_bounds__(GS_THREADS) void greedy_select_kernel(ArgmaxArgs a)
             return;
         }
         const int unf = a.unfinished[row];
-        const int64_t tok = unf ? (int64_t)i1 : (int64_t)a.pad;
+        int64_t tok = unf ? (int64_t)i1 : (int64_t)a.pad;
+        // decoder prompt: a forced column takes the prompt's token, scores 0 and leaves the row live (a row in its prompt has never finished)
+        const bool forced = prompt_forced(a.prompt, row, pos, a.V, tok);
         a.next_ids[row] = tok;
         if (pos < a.max_len) a.out_ids[(size_t)row * a.max_len + pos] = tok;
-        if (a.token_scores && pos < a.max_len) a.token_scores[(size_t)row * a.ts_ld + pos - 1] = unf ? -logf(se) : 0.f;
-        const int still = unf && !is_eos((int)tok);
+        if (a.token_scores && pos < a.max_len) a.token_scores[(size_t)row * a.ts_ld + pos - 1] = (unf && !forced) ? -logf(se) : 0.f;
+        const int still = forced ? 1 : (unf && !is_eos((int)tok));
         a.unfinished[row] = still;
         if (still) atomicAdd(a.n_unfinished, 1);
         if (a.top2) {
@@ -600,13 +602,14 @@ __global__ __launch_bounds__(256) void greedy_select_fused_kernel(ArgmaxArgs a) 
             for (int ww = 1; ww < 4; ++ww) lse_merge(lm, ls, rl[ww * 2], rl[ww * 2 + 1]);
         const int e0 = a.eos, e1 = a.n_eos_more > 0 ? a.eos_more[0] : -1, e2 = a.n_eos_more > 1 ? a.eos_more[1] : -1, e3 = a.n_eos_more > 2 ? a.eos_more[2] : -1;
         const int unf = a.unfinished[row];
-        const int64_t tok = unf ? (int64_t)i1 : (int64_t)a.pad;
+        int64_t tok = unf ? (int64_t)i1 : (int64_t)a.pad;
+        const bool forced = prompt_forced(a.prompt, row, pos, a.V, tok);      // decoder prompt, as greedy_select_kernel; the forced token is embedded below
         a.next_ids[row] = tok;
         ri[8] = (int)tok;
         if (pos < a.max_len) a.out_ids[(size_t)row * a.max_len + pos] = tok;
-        if (want_ts && pos < a.max_len) a.token_scores[(size_t)row * a.ts_ld + pos - 1] = unf ? (b1 - lm) - logf(ls) : 0.f;
+        if (want_ts && pos < a.max_len) a.token_scores[(size_t)row * a.ts_ld + pos - 1] = (unf && !forced) ? (b1 - lm) - logf(ls) : 0.f;
         const int t = (int)tok;
-        const int still = unf && !(t == e0 || t == e1 || t == e2 || t == e3);
+        const int still = forced ? 1 : (unf && !(t == e0 || t == e1 || t == e2 || t == e3));
         a.unfinished[row] = still;
         if (still) atomicAdd(a.n_unfinished, 1);
         if (a.top2) {

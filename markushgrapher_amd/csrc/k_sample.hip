@@ -128,8 +128,18 @@ __global__ __launch_bounds__(NT) void sample_select_kernel(SampleArgs a) {
     const int seq = QUEUE ? a.slots.img[row] : row;              // row of out_ids / token_scores / stream_ids
     int64_t tok = (int64_t)a.pad;
     float score = 0.f, b1 = 0.f, b2 = 0.f;
-    bool writer = tid == 0;                  // the thread that does the row's bookkeeping: thread 0 of a finished row, else the one that holds the draw
-    if (unf) {
+    bool writer = tid == 0;                  // the thread that does the row's bookkeeping: thread 0 of a finished or forced row, else the one that holds the draw
+    // decoder prompt (batch form): a row in a forced column neither scans nor draws - thread 0 writes the prompt's token with score 0 and
+    // the row stays live; it takes part in the step's counters exactly as a free row does
+    bool forced = false;
+    if (!QUEUE && a.prompt.ids) forced = pos < a.prompt.len[a.prompt.group > 1 ? row / a.prompt.group : row];
+    if (forced) {
+        // Every thread has read the step counter (pos) before thread 0 may advance it: the last workgroup to arrive increments *pos_dev in
+        // its bookkeeping below, and a thread of this workgroup that read it afterwards would no longer see a forced column.  (A free row
+        // has its scan's barriers between the two; a finished row never looks at pos again.)
+        __syncthreads();
+        if (tid == 0) prompt_forced(a.prompt, row, pos, a.V, tok);
+    } else if (unf) {
         const float* lg = a.logits + (size_t)row * a.ldl;
         const bool no_eos = pos < a.min_len;
         const int nq = (a.V + 3) >> 2;       // rows are padded to a multiple of 32 floats, so the last float4 is readable
@@ -270,7 +280,7 @@ __global__ __launch_bounds__(NT) void sample_select_kernel(SampleArgs a) {
         a.next_ids[row] = tok;
         if (pos < a.max_len) a.out_ids[(size_t)row * a.max_len + pos] = tok;
         if (a.token_scores && pos < a.max_len) a.token_scores[(size_t)row * a.ts_ld + pos - 1] = unf ? score : 0.f;
-        const int still = unf && tok != (int64_t)a.eos;
+        const int still = forced ? 1 : (unf && tok != (int64_t)a.eos);
         a.unfinished[row] = still;
         if (still) atomicAdd(a.n_unfinished, 1);
         if (a.top2) {

@@ -412,6 +412,29 @@ struct SlotTable {
     int n_stop, stop[4], max_len;
     int nsamp = 1;     // sequences per image (greedy, beam and OCR queues: 1)
 };
+// Decoder prompt of the batch decode loops (mg_generate_prompted): while the column a row writes is below its prompt length, the
+// selection writes the prompt's token there instead of its own choice - the row stays unfinished whatever the token is (a forced EOS
+// does not end it), draws nothing and scores 0.0; from its first free column on it decodes as an unprompted row.  ids == null: no prompt.
+struct DecPrompt {
+    const int64_t* ids;      // [owners][ld]; an id outside [0, V) is replaced by 0 and counted in *bad
+    const int* len;          // [owners] forced columns of the owner's rows, 1 <= len <= ld
+    int ld;
+    int group;               // rows per owner: row r takes the prompt of owner r / group (samples of an image; 0 / 1: one prompt per row)
+    int* bad;                // nullable
+};
+// -> true: column `col` of `row` is forced, tok = its (checked) token
+MG_DEV bool prompt_forced(const DecPrompt& p, int row, int col, int V, int64_t& tok) {
+    if (!p.ids) return false;
+    const int o = p.group > 1 ? row / p.group : row;
+    if (col >= p.len[o]) return false;
+    int64_t t = p.ids[(size_t)o * p.ld + col];
+    if (t < 0 || t >= (int64_t)V) {
+        if (p.bad) atomicAdd(p.bad, 1);
+        t = 0;
+    }
+    tok = t;
+    return true;
+}
 struct ArgmaxArgs {
     const float* logits;     // [rows][ldl]
     int rows, V, ldl;
@@ -449,6 +472,7 @@ struct ArgmaxArgs {
     // fused form needs the lm_head partials made with TopOut::lse = 1
     float* token_scores;
     int ts_ld;               // columns per row of token_scores (max_len - 1)
+    DecPrompt prompt;        // batch forms only (slots.pos == null); ids null: none
 };
 void greedy_select(const ArgmaxArgs& a, mgStream_t stream);
 void greedy_select_fused(const ArgmaxArgs& a, mgStream_t stream);
@@ -478,6 +502,7 @@ struct SampleArgs {
     float* token_scores;     // nullable, [rows][ts_ld]: log-probability of the drawn token under the warped distribution, column pos - 1
     int ts_ld;
     SlotTable slots;         // continuous decoding (slots.pos == null: batch form)
+    DecPrompt prompt;        // batch form only; a forced row makes no draw
 };
 bool sample_select_supported(int V);     // the row is held in registers: V <= 36 864
 void sample_select(const SampleArgs& a, mgStream_t stream);
@@ -502,12 +527,14 @@ void slot_refill(const SlotTable& s, int64_t* next_ids, int* unfinished, int row
 // hold the same values; pos == null: batch form (one position for all images, the batch's continue flag in counters[0])
 struct BeamSlots { const int* pos; const int* live; };
 size_t beam_state_bytes(int B, int K, int max_len);
+// prompt (nullable; batch form, one owner per image, group ignored): the K rows of image b start holding its prompt (stock writes
+// input_ids into running_sequences and sequences, utils.py:3326-3327), V bounds its ids
 void beam_init(void* state, int B, int K, int max_len, int pad, int eos, int start, int64_t* next_ids, int* anc, int T_cap,
-               int* counters, mgStream_t stream);
+               int* counters, mgStream_t stream, const DecPrompt* prompt = nullptr, int V = 0);
 float beam_length_divisor(int cur_len, float length_penalty);
 void beam_step(void* state, const float* logits, int ldl, int V, int B, int K, int max_len, int cur_len, const int* tdev,
                const float* div_table, int eos, int min_len, float length_penalty, int early_stopping, int64_t* next_ids,
-               int* beam_idx, int* counters, mgStream_t stream, const BeamSlots* slots = nullptr);
+               int* beam_idx, int* counters, mgStream_t stream, const BeamSlots* slots = nullptr, const DecPrompt* prompt = nullptr);
 // n-best output of an image's finished hypotheses (best first).  Hypothesis h < num_return of image i is output row i * num_return + h:
 // out_ids [rows][max_len], scores [rows] (sequence scores), and, nullable, beam_indices [rows][max_len - 1] (stock semantics: the flat row
 // image * K + beam each token was chosen from, -1 past the hypothesis' length) and token_scores [rows][max_len - 1] (the processed

@@ -39,6 +39,11 @@ class MgSampleOpts(C.Structure):
                 ("num_return", C.c_int), ("token_scores", C.c_void_p)]
 
 
+class MgDecoderPrompt(C.Structure):
+    """include/mgrapher.h mg_decoder_prompt: ids [B][ld] i64 on the device, the lengths [B] i32 on the host."""
+    _fields_ = [("ids", C.c_void_p), ("len_host", C.c_void_p), ("ld", C.c_int)]
+
+
 class TorchMem:
     """Device memory carried by torch tensors on one GPU."""
 
@@ -154,6 +159,8 @@ class Engine:
         L.mg_generate_sampled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p,
                                           C.POINTER(MgSampleOpts)]
+        L.mg_prompted_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+        L.mg_generate_prompted.argtypes = L.mg_generate_scored.argtypes + [C.POINTER(MgSampleOpts), C.POINTER(MgDecoderPrompt)]
         L.mg_stream_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         L.mg_generate_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + \
                                         [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.POINTER(C.c_long)]
@@ -292,11 +299,14 @@ class Engine:
         k = self.lib.mg_debug_bucket_table(self.model, which, out, n)
         return np.array(out[:k], dtype=np.int32)
 
-    def workspace(self, B, L, num_beams, max_length, T, M_e1=0, sampled=False):
+    def workspace(self, B, L, num_beams, max_length, T, M_e1=0, sampled=False, prompted=False):
         """The context's workspace, grown to what the call needs.  sampled: num_beams is the samples per image of a generate_sampled call
-        (mg_sampled_workspace_bytes: its rows choose the cross-attention form as greedy rows)."""
+        (mg_sampled_workspace_bytes: its rows choose the cross-attention form as greedy rows).  prompted: a call with a decoder prompt
+        (mg_prompted_workspace_bytes: the unprompted size plus the prompt lengths)."""
         need = C.c_size_t()
-        if sampled:
+        if prompted:
+            self._chk(self.lib.mg_prompted_workspace_bytes(self.model, B, L, num_beams, max_length, M_e1, 1 if sampled else 0, C.byref(need)))
+        elif sampled:
             self._chk(self.lib.mg_sampled_workspace_bytes(self.model, B, L, num_beams, max_length, M_e1, C.byref(need)))
         else:
             self._chk(self.lib.mg_workspace_bytes(self.model, B, L, num_beams, max_length, T, M_e1, C.byref(need)))
@@ -476,13 +486,45 @@ class Engine:
                          self.mem.ptr(bi).value if bi is not None else None)
         return opts, ts, ss, bi
 
+    def _prompt(self, decoder_prompt, decoder_prompt_len, B):
+        """decoder_prompt [B, P] int64 (+ decoder_prompt_len [B], default all P) -> MgDecoderPrompt, or None without a prompt.  The ids live
+        in a buffer kept per (B, P) with the context's persistent buffers: the captured decode step holds its address, so repeated calls
+        of one shape replay the step instead of re-capturing it.  Ranges are checked by the library (MG_E_ARG)."""
+        if decoder_prompt is None:
+            if decoder_prompt_len is not None:
+                raise ValueError("decoder_prompt_len needs decoder_prompt")
+            return None
+        src = self.mem.asarray(decoder_prompt, np.int64)
+        if len(src.shape) != 2 or int(src.shape[0]) != B or int(src.shape[1]) < 1:
+            raise ValueError(f"decoder_prompt must be [B = {B}, P >= 1], got {tuple(src.shape)}")
+        P = int(src.shape[1])
+        if decoder_prompt_len is None:
+            lens = np.full((B,), P, np.int32)
+        else:
+            if hasattr(decoder_prompt_len, "detach"):
+                decoder_prompt_len = decoder_prompt_len.detach().cpu().numpy()
+            lens = np.ascontiguousarray(np.asarray(decoder_prompt_len).reshape(-1).astype(np.int32))
+            if lens.shape[0] != B:
+                raise ValueError(f"decoder_prompt_len must hold B = {B} lengths, got {lens.shape[0]}")
+        cache = self.__dict__.setdefault("_prompt_buf", {})
+        if (B, P) not in cache:
+            if len(cache) > 8:
+                cache.clear()
+            cache[(B, P)] = self.mem.zeros((B, P), np.int64)
+        buf = cache[(B, P)]
+        buf[...] = src
+        self._prompt_keep = (buf, lens)
+        return MgDecoderPrompt(self.mem.ptr(buf).value, lens.ctypes.data, P)
+
     def generate_sampled(self, input_ids, bbox, attention_mask, pixel_values, max_length=512, min_length=0, temperature=1.0, top_k=0,
-                         top_p=1.0, seed=0, num_return=1, stream_ids=None, return_scores=False, return_top2=False, e1=None):
+                         top_p=1.0, seed=0, num_return=1, stream_ids=None, return_scores=False, return_top2=False, e1=None,
+                         decoder_prompt=None, decoder_prompt_len=None):
         """Sampled decoding (include/mgrapher.h mg_generate_sampled): temperature, top-k (0 = off), top-p (1 = off) in stock's order, one
         Philox4x32-10 draw per live row and step at counter (stream id, column) under the key `seed`.  -> (ids [B * num_return, cols],
         cols, token_scores [B * num_return, cols - 1] or None[, top2]): row b * num_return + j is sample j of image b.  stream_ids
         [B * num_return] (default: the row index) name the rows' random streams: a row's draws depend on (seed, stream id, column) and its own
-        logits only."""
+        logits only.  decoder_prompt [B, P] / decoder_prompt_len [B]: image b's samples all start with its prompt (mg_generate_prompted);
+        forced columns draw nothing and score 0.0."""
         ids, bb, am, pv, B, L = self._inputs(input_ids, bbox, attention_mask, pixel_values)
         nr = int(num_return)
         if nr < 1:
@@ -497,7 +539,8 @@ class Engine:
         if R > self.MAX_LIVE_ROWS:
             raise MgError(f"generate_sampled: B * num_return = {R} live sequences exceeds the supported {self.MAX_LIVE_ROWS}; split the batch")
         e1t, M = self._e1(e1, B)
-        ws, nb = self.workspace(B, L, nr, max_length, 0, M, sampled=True)
+        prompt = self._prompt(decoder_prompt, decoder_prompt_len, B)
+        ws, nb = self.workspace(B, L, nr, max_length, 0, M, sampled=True, prompted=prompt is not None)
         # persistent output / stream-id buffers: the captured decode step holds their addresses (see generate)
         cache = self._samp_out
         okey = (R, max_length)
@@ -519,10 +562,17 @@ class Engine:
                             self.mem.ptr(sid).value if sid is not None else None, nr,
                             self.mem.ptr(c["ts"]).value if return_scores else None)
         cols = C.c_int(0)
-        self._chk(self.lib.mg_generate_sampled(
-            self.model, self.mem.stream(), self.mem.ptr(ws), nb, self.mem.ptr(ids), self.mem.ptr(bb),
-            self.mem.ptr(am) if am is not None else None, self.mem.ptr(pv), self.mem.ptr(e1t) if e1t is not None else None, M, B, L,
-            max_length, min_length, self.mem.ptr(c["ids"]), C.byref(cols), self.mem.ptr(top2) if top2 is not None else None, C.byref(opts)))
+        if prompt is not None:
+            self._chk(self.lib.mg_generate_prompted(
+                self.model, self.mem.stream(), self.mem.ptr(ws), nb, self.mem.ptr(ids), self.mem.ptr(bb),
+                self.mem.ptr(am) if am is not None else None, self.mem.ptr(pv), self.mem.ptr(e1t) if e1t is not None else None, M, B, L,
+                1, max_length, min_length, C.c_float(1.0), 0, self.mem.ptr(c["ids"]), C.byref(cols), None,
+                self.mem.ptr(top2) if top2 is not None else None, None, C.byref(opts), C.byref(prompt)))
+        else:
+            self._chk(self.lib.mg_generate_sampled(
+                self.model, self.mem.stream(), self.mem.ptr(ws), nb, self.mem.ptr(ids), self.mem.ptr(bb),
+                self.mem.ptr(am) if am is not None else None, self.mem.ptr(pv), self.mem.ptr(e1t) if e1t is not None else None, M, B, L,
+                max_length, min_length, self.mem.ptr(c["ids"]), C.byref(cols), self.mem.ptr(top2) if top2 is not None else None, C.byref(opts)))
         n = cols.value
         res = (self.mem.copy(c["ids"][:, :n]), n, self.mem.copy(c["ts"][:, :n - 1]) if return_scores else None)
         return res + (top2,) if return_top2 else res
@@ -652,11 +702,15 @@ class Engine:
         return self.mem.copy(out[0]), self.mem.copy(out[1]), self.mem.copy(out[2]), int(steps.value)
 
     def generate(self, input_ids, bbox, attention_mask, pixel_values, num_beams=1, max_length=512, min_length=0,
-                 length_penalty=1.0, early_stopping=False, return_top2=False, e1=None, num_return=1, return_scores=False):
+                 length_penalty=1.0, early_stopping=False, return_top2=False, e1=None, num_return=1, return_scores=False,
+                 decoder_prompt=None, decoder_prompt_len=None):
         """-> (ids [B, cols], scores [B] (beam: sequences_scores), top2 or None).  num_return (beam: 1 .. num_beams): the n-best list,
         ids [B * num_return, cols] and scores [B * num_return], hypotheses of an image consecutive, best first; cols = the longest
         returned hypothesis'.  return_scores: a fourth item {"token_scores": [rows, cols - 1], "beam_indices": [rows, cols - 1] (beam) or
-        None} - include/mgrapher.h mg_generate_scored."""
+        None} - include/mgrapher.h mg_generate_scored.
+        decoder_prompt [B, P] int64 / decoder_prompt_len [B] (default all P): image b's rows start with decoder_prompt[b, :len[b]] and
+        decode freely from there (include/mgrapher.h mg_generate_prompted); the returned ids include the prompt, token_scores are 0.0 in
+        its columns."""
         ids, bb, am, pv, B, L = self._inputs(input_ids, bbox, attention_mask, pixel_values)
         nr = int(num_return)
         if not 1 <= nr <= num_beams:
@@ -665,7 +719,8 @@ class Engine:
         if B * num_beams > self.MAX_LIVE_ROWS:
             raise MgError(f"generate: B * num_beams = {B * num_beams} live sequences exceeds the supported "
                           f"{self.MAX_LIVE_ROWS}; split the batch")
-        ws, nb = self.workspace(B, L, num_beams, max_length, 0, M)
+        prompt = self._prompt(decoder_prompt, decoder_prompt_len, B)
+        ws, nb = self.workspace(B, L, num_beams, max_length, 0, M, prompted=prompt is not None)
         # the id buffer is persistent per (B, max_length): the captured decode-step graph holds its address, so a stable
         # buffer lets later calls replay the graph instead of re-capturing; callers get a copy
         okey = (B * nr, max_length)
@@ -681,7 +736,10 @@ class Engine:
                 num_beams, max_length, min_length, C.c_float(length_penalty), 1 if early_stopping is True else 0,
                 self.mem.ptr(out), C.byref(cols), self.mem.ptr(scores), self.mem.ptr(top2) if top2 is not None else None)
         if nr == 1 and not return_scores:
-            self._chk(self.lib.mg_generate(*args))
+            if prompt is not None:
+                self._chk(self.lib.mg_generate_prompted(*args, None, None, C.byref(prompt)))
+            else:
+                self._chk(self.lib.mg_generate(*args))
             return self.mem.copy(out[:, :cols.value]), scores, top2
         beam = num_beams > 1
         opts, ts, _, bi = self._scored_out("batch", B * nr, max_length, beam)
@@ -689,7 +747,10 @@ class Engine:
         opts.seq_scores = self.mem.ptr(scores).value if beam else None
         if not return_scores:
             opts.token_scores = opts.beam_indices = None
-        self._chk(self.lib.mg_generate_scored(*args, C.byref(opts)))
+        if prompt is not None:
+            self._chk(self.lib.mg_generate_prompted(*args, C.byref(opts), None, C.byref(prompt)))
+        else:
+            self._chk(self.lib.mg_generate_scored(*args, C.byref(opts)))
         n = cols.value
         res = (self.mem.copy(out[:, :n]), scores, top2)
         if return_scores:

@@ -485,8 +485,66 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
             seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
         return temperature, int(top_k), top_p, int(seed)
 
+    def _decoder_prompt(self, kw, B, max_length, min_length):
+        """The decoder-prompt keywords of generate(), as stock treats them -> (prompt [B, P] int64 or None, lengths [B] int32 numpy or None,
+        P of an equal-length prompt (1 without one, None when ragged), max_length, min_length).
+          decoder_input_ids [B, P]: stock's start-token rule (_prepare_decoder_input_ids_for_generation) - if NO row starts with
+            decoder_start_token_id it is prepended (and a column of ones to the mask).
+          decoder_attention_mask [B, P]: the rows' lengths.  UDOP's pad id equals its start id, so padding cannot be read off the values;
+            each row must be a run of ones from column 0.  No mask: every row uses the full width.
+          max_new_tokens / min_new_tokens: max_length = P + max_new_tokens, min_length = P + min_new_tokens (min_new_tokens wins over
+            min_length, as in stock); per-row limits are not built, so ragged prompts refuse them."""
+        dec = kw.pop("decoder_input_ids", None)
+        dmask = kw.pop("decoder_attention_mask", None)
+        max_new, min_new = kw.pop("max_new_tokens", None), kw.pop("min_new_tokens", None)
+        lens, P = None, 1
+        if dec is None:
+            if dmask is not None:
+                raise ValueError("`decoder_attention_mask` needs `decoder_input_ids`")
+        else:
+            dec = torch.as_tensor(dec).to(torch.int64)
+            if dec.dim() != 2 or int(dec.shape[0]) != B or int(dec.shape[1]) < 1:
+                raise ValueError(f"`decoder_input_ids` must be [{B}, P >= 1], got {tuple(dec.shape)}")
+            if dmask is not None:
+                dmask = torch.as_tensor(dmask).to(dec.device)
+                if tuple(dmask.shape) != tuple(dec.shape):
+                    raise ValueError(f"`decoder_attention_mask` must have the shape of `decoder_input_ids` {tuple(dec.shape)}, got {tuple(dmask.shape)}")
+                dmask = (dmask != 0).to(torch.int64)
+            start = int(self.config.decoder_start_token_id)
+            if bool((dec[:, 0] != start).all()):
+                dec = torch.cat([torch.full_like(dec[:, :1], start), dec], dim=-1)
+                if dmask is not None:
+                    dmask = torch.cat([torch.ones_like(dmask[:, :1]), dmask], dim=-1)
+            P = int(dec.shape[1])
+            if dmask is not None:
+                n = dmask.sum(-1)
+                run = (torch.arange(P, device=dmask.device)[None, :] < n[:, None]).to(torch.int64)
+                if bool((n < 1).any()) or not bool((dmask == run).all()):
+                    raise ValueError("every row of `decoder_attention_mask` must be a run of ones from column 0 (the prompt's length); "
+                                     "left padding and holes are not supported")
+                lens = n.cpu().numpy().astype(np.int32)
+                if bool((lens == lens[0]).all()):      # equal lengths: the common width is the prompt
+                    P = int(lens[0])
+                    dec, lens = dec[:, :P].contiguous(), None
+                else:
+                    P = None
+        if (max_new is not None or min_new is not None) and P is None:
+            raise ValueError("`max_new_tokens` / `min_new_tokens` with prompts of different lengths need per-row limits, which are not built; "
+                             "pass `max_length` / `min_length`")
+        if max_new is not None:
+            max_length = P + int(max_new)
+        if min_new is not None:
+            min_length = P + int(min_new)
+        max_length = int(max_length or self.config.max_length)
+        if dec is not None:
+            longest = int(dec.shape[1]) if lens is None else int(lens.max())
+            if longest >= max_length:
+                raise ValueError(f"the decoder prompt has {longest} tokens but `max_length` is {max_length}: nothing would be generated; "
+                                 "raise `max_length` or pass `max_new_tokens`")
+        return dec, lens, P, max_length, int(min_length)
+
     def _generate_sampled(self, input_ids, bbox, pixel_values, attention_mask, num_beams, max_length, min_length, e1, num_return, as_dict,
-                          want_scores, want_logits, kw):
+                          want_scores, want_logits, kw, prompt=(None, None, 1)):
         """generate(do_sample=True): stock `_sample` with the temperature / top-k / top-p warpers, drawn on the device
         (include/mgrapher.h mg_generate_sampled).  temperature=1.0, top_k=None (generation_config.top_k if the model has one, else stock's
         default 50; 0 = off), top_p=1.0, num_return_sequences=1, seed=None, stream_ids=None.
@@ -505,7 +563,8 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
         max_length = int(max_length or self.config.max_length)
         attention_mask = self._default_mask(input_ids, attention_mask)
         skw = dict(max_length=max_length, min_length=int(min_length), temperature=temperature, top_k=int(top_k), top_p=top_p, seed=int(seed),
-                   num_return=num_return, stream_ids=stream_ids, e1=e1)
+                   num_return=num_return, stream_ids=stream_ids, e1=e1, decoder_prompt=prompt[0], decoder_prompt_len=prompt[1])
+        first = prompt[2] - 1 if prompt[2] else 0      # output_scores / output_logits hold the free steps only, as stock's do
         if not as_dict:
             return eng.generate_sampled(input_ids, bbox, attention_mask, pixel_values, **skw)[0]
         cap = None
@@ -521,12 +580,12 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
             steps = int(ids.shape[1]) - 1
             raw = cap[:steps]
             if want_logits:
-                out.logits = tuple(raw[t].clone() for t in range(steps))
+                out.logits = tuple(raw[t].clone() for t in range(first, steps))
             if want_scores:
                 sc = raw.clone()
                 for t in range(min(steps, max(0, int(min_length) - 1))):
                     sc[t, :, self.config.eos_token_id] = -float("inf")
-                out.scores = tuple(sc[t] / temperature for t in range(steps))
+                out.scores = tuple(sc[t] / temperature for t in range(first, steps))
         return out
 
     @torch.no_grad()
@@ -534,14 +593,22 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
                  max_length=None, min_length=0, length_penalty=1.0, early_stopping=False, do_sample=False, e1=None, **kw):
         """ref call: utils_evaluation.py:269-285 (`labels` arrives as a stray kwarg and is ignored).  Without an
         attention_mask the fork's transformers 4.34 base infers one from pad tokens (all ones at the reference's batch
-        size 1), which is what is reproduced here; pass a mask explicitly for padded batches."""
+        size 1), which is what is reproduced here; pass a mask explicitly for padded batches.
+        decoder_input_ids= [B, P] (with decoder_attention_mask= for prompts of different lengths): the answers start with the given tokens
+        and the model writes the rest, in all three decode modes (include/mgrapher.h mg_generate_prompted; rules: _decoder_prompt).  The
+        returned sequences include the prompt, token_scores are 0.0 in its columns, output_scores / output_logits hold the free steps only.
+        max_new_tokens= / min_new_tokens= count from the prompt's end (from the start token without one)."""
         num_return = int(kw.pop("num_return_sequences", None) or 1)
         as_dict = bool(kw.pop("return_dict_in_generate", False))
         want_scores, want_logits = bool(kw.pop("output_scores", False)), bool(kw.pop("output_logits", False))
         num_beams = int(num_beams)
+        dec, dec_len, P, max_length, min_length = self._decoder_prompt(kw, int(input_ids.shape[0]), max_length, min_length)
+        if dec is not None and P is None and (want_scores or want_logits):
+            raise ValueError("`output_scores` / `output_logits` with prompts of different lengths are not built: the tuples hold one entry "
+                             "per free step of the whole batch")
         if do_sample:
             return self._generate_sampled(input_ids, bbox, pixel_values, attention_mask, num_beams, max_length, min_length, e1, num_return,
-                                          as_dict, want_scores, want_logits, kw)
+                                          as_dict, want_scores, want_logits, kw, prompt=(dec, dec_len, P))
         if num_beams == 1 and num_return > 1:
             raise ValueError(f"Greedy methods without beam search do not support `num_return_sequences` different than 1 (got {num_return}).")
         if num_return > num_beams:
@@ -551,7 +618,8 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
         max_length = int(max_length or self.config.max_length)
         attention_mask = self._default_mask(input_ids, attention_mask)
         gkw = dict(num_beams=num_beams, max_length=max_length, min_length=int(min_length), length_penalty=float(length_penalty),
-                   early_stopping=early_stopping, e1=e1)
+                   early_stopping=early_stopping, e1=e1, decoder_prompt=dec, decoder_prompt_len=dec_len)
+        first = P - 1 if P else 0      # output_scores / output_logits hold the free steps only, as stock's do
         if not as_dict:
             ids, _, _ = eng.generate(input_ids, bbox, attention_mask, pixel_values, num_return=num_return, **gkw)
             return ids
@@ -573,7 +641,7 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
             steps = int(ids.shape[1]) - 1
             raw = cap[:steps]
             if want_logits:
-                out.logits = tuple(raw[t].clone() for t in range(steps))
+                out.logits = tuple(raw[t].clone() for t in range(first, steps))
             if want_scores:
                 # stock's processed scores: log-softmax first for beam search (utils.py:3388-3389), then MinLength (EOS at -inf while
                 # the sequence is shorter than min_length)
@@ -581,7 +649,7 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
                 eos = self.config.eos_token_id
                 for t in range(min(steps, max(0, int(min_length) - 1))):
                     sc[t, :, eos] = -float("inf")
-                out.scores = tuple(sc[t] for t in range(steps))
+                out.scores = tuple(sc[t] for t in range(first, steps))
         return out
 
     def compute_transition_scores(self, sequences, scores, beam_indices=None, normalize_logits=False):
@@ -651,6 +719,9 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
         max_length = int(max_length or self.config.max_length)
         feats = []
         for e in encodings:
+            if e.get("decoder_input_ids") is not None:
+                raise ValueError("generate_queue: an encoding carries `decoder_input_ids`; the queue forms do not take a decoder prompt "
+                                 "(use generate())")
             ids = torch.as_tensor(e["input_ids"]).reshape(-1).cpu()
             feats.append({"input_ids": ids, "bbox": torch.as_tensor(e["bbox"]).reshape(-1, 4).cpu().to(torch.float32)})
         batch = collate_for_generate(feats)
