@@ -253,6 +253,47 @@ int mg_generate_prompted(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
                          float* out_scores, float* step_top2, const mg_gen_opts* opts, const mg_sample_opts* samp,
                          const mg_decoder_prompt* prompt);
 
+/* Constrained decoding: a set of allowed tokens that depends on what a row has emitted so far, as a finite automaton over token classes
+ * that the selection kernels consult and advance inside the captured decode step.  Token t has class cls[t]; a row in state s may emit t
+ * iff table[s][cls[t]] >= 0, and that entry is its next state.  The LAST state is the sink: it allows EOS only, and EOS is a class of its
+ * own.  Banned tokens and multi-token words, tokens banned at the first free position and "answer with one of these sequences" all
+ * compile to this (markushgrapher_amd/constraint.py builds them and checks the conventions).
+ *   mg_generate_constrained = mg_generate_prompted plus the constraint; constraint == NULL is exactly mg_generate_prompted.  Greedy
+ * (num_beams = 1, samp NULL), beam-search and sampled calls take it; all rows of an image (its beams or samples) start from start_host[b], the image's state at
+ * its first free column - with a decoder prompt the caller passes the state after the prompt: forced columns leave the state untouched.
+ *   - A disallowed token is treated exactly as MinLength's suppressed EOS: it cannot be chosen, is left out of step_top2 and out of the
+ *     normaliser of token_scores (greedy), and becomes -inf before temperature, top-k and top-p (sampled); draws keep their counter and stream.
+ *   - A constrained greedy call runs the unfused selection tail, as sampled calls do.
+ *   - A finished row emits pad and keeps its state.
+ *   - Empty allowed set (MinLength and the state together leave nothing, e.g. an EOS-only state below min_length): the row emits EOS and
+ *     ends, moves to the sink, scores 0.0, draws nothing; the call completes and returns MG_E_INPUT, as it does for bad ids.
+ *   cls, table and their sizes are part of the captured step's key: keep them in place (and refill them in place for another automaton of
+ * the same sizes) and a later call of the same shape replays the graph.  States and start states are device data, reset by every call.
+ *   Checks (MG_E_ARG): non-null pointers, 1 <= n_classes <= 4096, n_states >= 2, n_states * n_classes <= 2^24, every start_host[b] in
+ * [0, n_states).  The ENTRIES of cls (< n_classes) and table (-1 or < n_states) are NOT checked here: they live on the device; the Python
+ * layer checks them on the host before it uploads them (TokenAutomaton's constructor).  A constraint while mg_debug_decode_capture's forced
+ * ids are set: MG_E_UNSUPPORTED.
+ *   WORKSPACE: mg_constrained_workspace_bytes = mg_prompted_workspace_bytes plus the [rows] states, the class row padded to the logits'
+ * row stride and the counter, which follow the prompted layout.
+ *   Beam search: the log-softmax stays over the raw logits and the mask sets a candidate's log-probability to -inf where MinLength's EOS is
+ * set (stock's order: log_softmax, then the processors); the states of an image's K rows are reordered with the beams.  There is no
+ * empty-set rule: -inf candidates are ranked, as in stock, and a beam that takes one moves to the sink.
+ *   NOT built: the queue forms (mg_generate_stream*) and the OCR stage
+ * under a constraint; the mask inside the fused lm_head epilogue; sparse tables for automata beyond 2^24 entries; forced_eos_token_id;
+ * repetition_penalty and no_repeat_ngram_size (they change logit values or need unbounded history: not masks). */
+typedef struct mg_constraint {
+    const uint16_t* cls;         /* [vocab] device */
+    const int32_t* table;        /* [n_states][n_classes] device */
+    int n_states, n_classes;
+    const int32_t* start_host;   /* [B] host: each image's state at its first free column */
+} mg_constraint;
+int mg_constrained_workspace_bytes(const mg_model* m, int B, int L, int rows_per_image, int max_length, int M_e1, int sampled, size_t* out_bytes);
+int mg_generate_constrained(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
+                            const uint8_t* attention_mask, const float* pixel_values, const float* e1, int M_e1, int B, int L, int num_beams,
+                            int max_length, int min_length, float length_penalty, int early_stopping, int64_t* out_ids, int* out_cols_host,
+                            float* out_scores, float* step_top2, const mg_gen_opts* opts, const mg_sample_opts* samp,
+                            const mg_decoder_prompt* prompt, const mg_constraint* constraint);
+
 /* Continuous greedy decoding of N images - what the reference's evaluation loop does one image at a time with
  * model.generate(**encoding, num_beams=1, max_length=512) until EOS (/root/reference/markushgrapher/utils/ocsr/utils_evaluation.py:140,
  * 269-285), for a whole queue of images: `slots` decode rows work through the queue, a row that ends (EOS / max_length) frees its
@@ -851,6 +892,39 @@ int mgk_beam_init_prompted(void* stream, void* state, int B, int K, int max_len,
 int mgk_beam_step_prompted(void* stream, void* state, const float* logits, int ldl, int V, int B, int K, int max_len, int cur_len, const int* tdev,
                            const float* div_table, int eos, int min_len, float length_penalty, int early_stopping, int64_t* next_ids,
                            int* beam_idx, int* counters, const int64_t* prompt_ids, const int* prompt_len, int prompt_ld);
+/* The selection step under a constraint (mg_generate_constrained; DecConstraint in csrc/mg_kernels.h), batch forms of the greedy scan and
+ * of the sampled selection (a slot table, the fused form or ptop with a constraint: MG_E_ARG).  All pointers device.  cls is padded to the
+ * logits' row stride ([ldl], the padding is never taken for a token); state [rows] is read and advanced in place; *empty counts the rows
+ * that met an empty allowed set.  Sizes are checked as mg_generate_constrained checks them, before any device work (MG_E_ARG).  The
+ * decoder prompt is optional (prompt_ids NULL: none): a forced column leaves the row's state untouched, as a finished row does.
+ * mgk_select_constrained = mgk_select_ex / mgk_select_prompted; mgk_sample_select_constrained = mgk_sample_select_prompted plus top2
+ * [rows][2] (nullable; with pos_dev the base of [max_len][rows][2]) - neither clears n_unfinished. */
+typedef struct mgk_constraint {
+    const uint16_t* cls;     /* [ldl] */
+    const int32_t* table;    /* [n_states][n_classes]: next state, -1 = not allowed */
+    int n_states, n_classes;
+    int32_t* state;          /* [rows] */
+    int32_t* empty;          /* [1] */
+} mgk_constraint;
+int mgk_select_constrained(void* stream, const mgk_select_desc* s, const mgk_constraint* con, const int64_t* prompt_ids, const int* prompt_len,
+                           int prompt_ld, int group, int* bad);
+/* Beam search under a constraint: mgk_beam_init_prompted / mgk_beam_step_prompted plus the constraint (prompt_ids NULL: no prompt; cls here
+ * is [V]).  init: con->state[b * K + k] = con_start[b] (con_start [B] device).  step: the log-softmax stays over the raw logits and a token
+ * the row's state does not allow gets the log-probability -inf where MinLength's EOS does; afterwards running beam k holds
+ * table[state of its parent][cls[token]], the sink where that entry is -1; a forced prompt column leaves the states untouched.  div_table
+ * [max_len + 1] is required.  *empty is not used: -inf candidates are what stock has there too. */
+int mgk_beam_init_constrained(void* stream, void* state, int B, int K, int max_len, int pad, int eos, int start, int64_t* next_ids, int* anc,
+                              int T_cap, int* counters, const int64_t* prompt_ids, const int* prompt_len, int prompt_ld, int V, int* bad,
+                              const mgk_constraint* con, const int* con_start);
+int mgk_beam_step_constrained(void* stream, void* state, const float* logits, int ldl, int V, int B, int K, int max_len, int cur_len,
+                              const int* tdev, const float* div_table, int eos, int min_len, float length_penalty, int early_stopping,
+                              int64_t* next_ids, int* beam_idx, int* counters, const int64_t* prompt_ids, const int* prompt_len, int prompt_ld,
+                              const mgk_constraint* con);
+int mgk_sample_select_constrained(void* stream, const float* logits, int rows, int V, int ldl, int eos, int pad, int min_len, float temperature,
+                                  int top_k, float top_p, uint64_t seed, const uint64_t* stream_ids, int64_t* next_ids, int64_t* out_ids,
+                                  int max_len, int pos, const int* pos_dev, int* unfinished, int* n_unfinished, int* step_ctr, float* token_scores,
+                                  int ts_ld, float* top2, const mgk_constraint* con, const int64_t* prompt_ids, const int* prompt_len,
+                                  int prompt_ld, int group, int* bad);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
  * ChemicalOCR stage ("next" row f-1).  Replaces, for the OCR pass that produces the cells the main model

@@ -334,9 +334,18 @@ static SlotTable slot_table(const mgk_slot_table* t) {
     for (int k = 0; k < 4; ++k) s.stop[k] = t->stop[k];
     return s;
 }
-static int select_impl(void* stream, const mgk_select_desc* s, const DecPrompt& prompt) {
+// the operator entries' constraint -> DecConstraint; MG_E_ARG before any device work (sizes as mg_generate_constrained checks them)
+static int dec_constraint(const mgk_constraint* c, DecConstraint* out) {
+    if (!c || !c->cls || !c->table || !c->state || !c->empty) return MG_E_ARG;
+    if (c->n_classes < 1 || c->n_classes > DEC_CON_MAX_CLASSES || c->n_states < 2) return MG_E_ARG;
+    if ((long long)c->n_states * c->n_classes > (1ll << 24)) return MG_E_ARG;
+    *out = DecConstraint{c->cls, c->table, c->n_states, c->n_classes, c->state, c->empty};
+    return MG_OK;
+}
+static int select_impl(void* stream, const mgk_select_desc* s, const DecPrompt& prompt, const DecConstraint& con = DecConstraint{}) {
     if (!s || !s->next_ids || !s->out_ids || !s->unfinished) return MG_E_ARG;
     const bool queue = s->slots.pos != nullptr;
+    if (con.cls && (queue || s->fused || s->ptop)) return MG_E_ARG;      // (a constraint belongs to the batch form of the scan: no slot table, no ptop)
     if (prompt.ids && (queue || !prompt.len || prompt.ld < 1 || prompt.group < 0)) return MG_E_ARG;      // (a prompt belongs to the batch forms)
     if (s->fused && queue) return MG_E_ARG;                              // (the fused tail has no queue form)
     if (queue ? (!s->slots.img || !s->slots.ctr || !s->slots.out_len) : !s->n_unfinished) return MG_E_ARG;
@@ -363,6 +372,7 @@ static int select_impl(void* stream, const mgk_select_desc* s, const DecPrompt& 
     a.gain = s->gain; a.x_pk = (uint16_t*)s->x_pk; a.x2_pk = (uint16_t*)s->x2_pk; a.x2_ld = s->x2_ld; a.x2_col0 = s->x2_col0; a.d = s->d;
     a.eps = s->eps; a.token_scores = s->token_scores; a.ts_ld = s->ts_ld;
     a.prompt = prompt;
+    a.con = con;
     if (s->fused) greedy_select_fused(a, (mgStream_t)stream); else greedy_select(a, (mgStream_t)stream);
     return MG_OK;
 }
@@ -390,6 +400,38 @@ int mgk_sample_select_prompted(void* stream, const float* logits, int rows, int 
     a.n_unfinished = n_unfinished; a.step_ctr = step_ctr; a.token_scores = token_scores; a.ts_ld = ts_ld;
     a.prompt = DecPrompt{prompt_ids, prompt_len, prompt_ld, group, bad};
     sample_select(a, (mgStream_t)stream);      // (n_unfinished is not cleared: the caller sets it, the step_ctr path clears it)
+    return MG_OK;
+}
+// mgk_select_ex under a constraint (DecConstraint, mg_kernels.h), with an optional decoder prompt (prompt_ids null: none)
+int mgk_select_constrained(void* stream, const mgk_select_desc* s, const mgk_constraint* con, const int64_t* prompt_ids, const int* prompt_len,
+                           int prompt_ld, int group, int* bad) {
+    DecConstraint dc{};
+    const int rc = dec_constraint(con, &dc);
+    if (rc != MG_OK) return rc;
+    return select_impl(stream, s, prompt_ids ? DecPrompt{prompt_ids, prompt_len, prompt_ld, group, bad} : DecPrompt{}, dc);
+}
+// mgk_sample_select_prompted under a constraint (prompt_ids null: no prompt), top2 [rows][2] nullable as the engine's launch has it
+int mgk_sample_select_constrained(void* stream, const float* logits, int rows, int V, int ldl, int eos, int pad, int min_len, float temperature,
+                                  int top_k, float top_p, uint64_t seed, const uint64_t* stream_ids, int64_t* next_ids, int64_t* out_ids,
+                                  int max_len, int pos, const int* pos_dev, int* unfinished, int* n_unfinished, int* step_ctr, float* token_scores,
+                                  int ts_ld, float* top2, const mgk_constraint* con, const int64_t* prompt_ids, const int* prompt_len,
+                                  int prompt_ld, int group, int* bad) {
+    if (!logits || !next_ids || !out_ids || !unfinished || !n_unfinished || rows < 1 || ldl < V || (ldl & 3)) return MG_E_ARG;
+    if (!(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f)) return MG_E_ARG;
+    if (prompt_ids && (!prompt_len || prompt_ld < 1 || group < 0)) return MG_E_ARG;
+    DecConstraint dc{};
+    const int rc = dec_constraint(con, &dc);
+    if (rc != MG_OK) return rc;
+    if (rows > 256 || max_len < 1 || (token_scores && ts_ld < max_len - 1)) return MG_E_SHAPE;
+    if (!sample_select_supported(V)) return MG_E_UNSUPPORTED;
+    SampleArgs a{};
+    a.logits = logits; a.rows = rows; a.V = V; a.ldl = ldl; a.eos = eos; a.pad = pad; a.min_len = min_len;
+    a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.seed = seed; a.stream_ids = stream_ids;
+    a.next_ids = next_ids; a.out_ids = out_ids; a.max_len = max_len; a.pos = pos; a.pos_dev = pos_dev; a.unfinished = unfinished;
+    a.n_unfinished = n_unfinished; a.step_ctr = step_ctr; a.token_scores = token_scores; a.ts_ld = ts_ld; a.top2 = top2;
+    if (prompt_ids) a.prompt = DecPrompt{prompt_ids, prompt_len, prompt_ld, group, bad};
+    a.con = dc;
+    sample_select(a, (mgStream_t)stream);      // (n_unfinished is not cleared, as in mgk_sample_select_prompted)
     return MG_OK;
 }
 int mgk_sample_select_queue(void* stream, const float* logits, int rows, int V, int ldl, int eos, int pad, int min_len, float temperature,
@@ -523,6 +565,36 @@ int mgk_beam_step_prompted(void* stream, void* state, const float* logits, int l
     const DecPrompt pr{prompt_ids, prompt_len, prompt_ld, 1, nullptr};
     beam_step(state, logits, ldl, V, B, K, max_len, cur_len, tdev, div_table, eos, min_len, length_penalty, early_stopping, next_ids, beam_idx,
               counters, (mgStream_t)stream, nullptr, &pr);
+    return MG_OK;
+}
+// mgk_beam_init_prompted / mgk_beam_step_prompted under a constraint (the prompt is optional: prompt_ids null).  start [B] device: the
+// images' states at their first free columns; con->state [B * K] takes them at init and is reordered and advanced by every free step
+int mgk_beam_init_constrained(void* stream, void* state, int B, int K, int max_len, int pad, int eos, int start, int64_t* next_ids, int* anc,
+                              int T_cap, int* counters, const int64_t* prompt_ids, const int* prompt_len, int prompt_ld, int V, int* bad,
+                              const mgk_constraint* con, const int* con_start) {
+    if (!beam_geometry_ok(B, K, max_len) || T_cap < max_len - 1 || V < 2 * K) return MG_E_SHAPE;
+    if (prompt_ids && (!prompt_len || prompt_ld < 1)) return MG_E_ARG;
+    DecConstraint dc{};
+    const int rc = dec_constraint(con, &dc);
+    if (rc != MG_OK) return rc;
+    if (!con_start) return MG_E_ARG;
+    const DecPrompt pr{prompt_ids, prompt_len, prompt_ld, 1, bad};
+    beam_init(state, B, K, max_len, pad, eos, start, next_ids, anc, T_cap, counters, (mgStream_t)stream, prompt_ids ? &pr : nullptr, V, dc.state,
+              con_start);
+    return MG_OK;
+}
+int mgk_beam_step_constrained(void* stream, void* state, const float* logits, int ldl, int V, int B, int K, int max_len, int cur_len,
+                              const int* tdev, const float* div_table, int eos, int min_len, float length_penalty, int early_stopping,
+                              int64_t* next_ids, int* beam_idx, int* counters, const int64_t* prompt_ids, const int* prompt_len, int prompt_ld,
+                              const mgk_constraint* con) {
+    if (!beam_geometry_ok(B, K, max_len) || V < 2 * K || ldl < V) return MG_E_SHAPE;
+    if (!div_table || (prompt_ids && (!prompt_len || prompt_ld < 1))) return MG_E_ARG;
+    DecConstraint dc{};
+    const int rc = dec_constraint(con, &dc);
+    if (rc != MG_OK) return rc;
+    const DecPrompt pr{prompt_ids, prompt_len, prompt_ld, 1, nullptr};
+    beam_step(state, logits, ldl, V, B, K, max_len, cur_len, tdev, div_table, eos, min_len, length_penalty, early_stopping, next_ids, beam_idx,
+              counters, (mgStream_t)stream, nullptr, prompt_ids ? &pr : nullptr, &dc);
     return MG_OK;
 }
 int mgk_beam_reorder_anc(void* stream, int* anc, const int* beam_idx, int rows, int t_written, const int* tdev, const int* counters,

@@ -67,8 +67,12 @@ struct BatchStepKey {        // mg_generate / mg_generate_sampled
     // prompted calls (mg_generate_prompted): the selection launches hold the prompt's pointers (the lengths are device data: not part of the key)
     const void *prompt_ids, *prompt_len;
     int prompt_ld;
+    // constrained calls (mg_generate_constrained): the caller's tables and their sizes (states and start states are device data)
+    const void *con_cls, *con_table;
+    int con_states, con_classes;
     MG_KEY_MEMBERS(BatchStepKey, ws, out_ids, step_top2, stream, B, L, K, max_length, min_length, early_stopping, M_e1, length_penalty,
-                   token_scores, num_return, top_k, temperature, top_p, seed, stream_ids, prompt_ids, prompt_len, prompt_ld)
+                   token_scores, num_return, top_k, temperature, top_p, seed, stream_ids, prompt_ids, prompt_len, prompt_ld, con_cls, con_table,
+                   con_states, con_classes)
 };
 struct QueueStepKey {        // mg_generate_stream*: greedy, sampled and beam queues
     const void *ws, *out_ids, *out_len, *stream;
@@ -123,6 +127,7 @@ struct mg_model {
     void reset_step_graphs() { step_graph.reset(); stream_graph.reset(); }
     std::vector<float> beam_div_host;
     std::vector<int32_t> prompt_len_host;           // mg_generate_prompted: the validated lengths, source of the call's upload
+    std::vector<int32_t> con_start_host;            // mg_generate_constrained: every row's start state, source of the call's upload
     int use_graph = 1;
     bool graph_active = false;
     // Greedy decoding with the weight-absorbed cross-attention (k_xattn.hip): a layer streams the encoder states once instead of its K and V.
@@ -665,6 +670,7 @@ struct DecodeCtx : DecodeBufs {
     BeamOut nbest;
     const mg_sample_opts* samp;   // sampled call (mg_generate_sampled, mg_generate_stream_sampled): the selection is sample_select; rows of an image read its K/V through slots.pool
     DecPrompt prompt;             // mg_generate_prompted (batch forms; ids null: none): greedy / sampled per row (group = samples per image), beam per image
+    DecConstraint con;            // mg_generate_constrained (batch forms; cls null: none): one state per row (greedy, sampled) / per beam row
 };
 
 // Decode step, 6 launches per layer: QKV -> self-attention -> [O residual | cross-Q] -> cross-attention ->
@@ -802,6 +808,7 @@ static void decode_step(mg_model* m, const DecodeCtx& c, int t, const int* tdev,
         g.slots = c.slots;
         g.token_scores = c.token_scores; g.ts_ld = max_length - 1;
         g.prompt = c.prompt;
+        g.con = c.con;
         if (c.samp) {
             SampleArgs sa{};
             sa.logits = c.logits; sa.rows = R; sa.V = m->V; sa.ldl = ldl; sa.eos = g.eos; sa.pad = g.pad; sa.min_len = min_length;
@@ -811,6 +818,7 @@ static void decode_step(mg_model* m, const DecodeCtx& c, int t, const int* tdev,
             sa.step_ctr = g.step_ctr; sa.token_scores = c.token_scores; sa.ts_ld = max_length - 1;
             sa.slots = c.slots;            // queue form: the row's column, output row and random stream come from the slot table
             sa.prompt = c.prompt;
+            sa.con = c.con;
             sample_select(sa, st);
         } else if (fused_tail) {
             g.ptop = c.ptop; g.stopv = c.stopv; g.ntiles = ldl / 32;
@@ -834,7 +842,7 @@ static void decode_step(mg_model* m, const DecodeCtx& c, int t, const int* tdev,
                         c.out_scores, c.slots.ctr, true, st, &c.nbest);
     } else {
         beam_step(c.beam_state, c.logits, ldl, m->V, B, K, max_length, t + 1, tdev, c.beam_div, m->c.eos_token_id, min_length,
-                  length_penalty, early_stopping, c.next_ids, c.beam_idx, counters, st, nullptr, &c.prompt);
+                  length_penalty, early_stopping, c.next_ids, c.beam_idx, counters, st, nullptr, &c.prompt, &c.con);
         beam_reorder_anc(c.anc, c.beam_idx, R, tdev ? max_length - 1 : t + 1, tdev, counters, st);
     }
     if (K > 1 && !stream) MG_LAUNCH(step_end_kernel, dim3(1), dim3(64), 0, st, counters, 0);
@@ -1431,6 +1439,10 @@ int mg_generate(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int6
 }  // extern "C"
 
 static size_t prompt_ws_bytes(int B) { return align_up((size_t)B * sizeof(int32_t), 256); }      // mg_generate_prompted: the lengths, behind the unprompted layout
+// mg_generate_constrained, behind the prompted layout: the rows' states [rows], the class row padded to the logits' stride, the counter
+static size_t con_state_bytes(int rows) { return align_up((size_t)rows * sizeof(int32_t), 256); }
+static size_t con_cls_bytes(int V) { return align_up((size_t)round_up(V, 32) * sizeof(uint16_t), 256); }
+static size_t con_ws_bytes(int rows, int V) { return con_state_bytes(rows) + con_cls_bytes(V) + 256; }
 
 // owner[r] = r / group: the image whose encoder states row r of a sampled call reads
 __global__ void row_owner_kernel(int* owner, int rows, int group) {
@@ -1445,7 +1457,7 @@ static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
                          const uint8_t* attention_mask, const float* pixel_values, const float* e1, int M_e1, int B, int L, int num_beams,
                          int max_length, int min_length, float length_penalty, int early_stopping, int64_t* out_ids, int* out_cols_host,
                          float* out_scores, float* step_top2, const mg_gen_opts* opts, const mg_sample_opts* samp, const char* who,
-                         const mg_decoder_prompt* prompt = nullptr) {
+                         const mg_decoder_prompt* prompt = nullptr, const mg_constraint* con = nullptr) {
     entry_drain();
     if (!m || !out_ids || !out_cols_host) return fail(MG_E_ARG, "%s: null argument", who);
     std::unique_lock<std::recursive_mutex> call_lock(m->call_mu, std::try_to_lock);      // MG_ONE_CALL under the entry's own name
@@ -1483,6 +1495,20 @@ static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
                 return fail(MG_E_ARG, "%s: decoder prompt length of image %d (%d) must be below max_length (%d)", who, b, len, max_length);
         }
     }
+    if (con) {
+        if (!con->cls || !con->table || !con->start_host) return fail(MG_E_ARG, "%s: constraint needs cls, table and start_host", who);
+        if (B < 1) return fail(MG_E_ARG, "%s: B must be >= 1", who);
+        if (con->n_classes < 1 || con->n_classes > DEC_CON_MAX_CLASSES)
+            return fail(MG_E_ARG, "%s: constraint n_classes (%d) must be in [1, %d]", who, con->n_classes, DEC_CON_MAX_CLASSES);
+        if (con->n_states < 2) return fail(MG_E_ARG, "%s: constraint n_states (%d) must be >= 2 (the last state is the sink)", who, con->n_states);
+        if ((long long)con->n_states * con->n_classes > (1ll << 24))
+            return fail(MG_E_ARG, "%s: constraint table of %d x %d entries exceeds 2^24", who, con->n_states, con->n_classes);
+        for (int b = 0; b < B; ++b)
+            if (con->start_host[b] < 0 || con->start_host[b] >= con->n_states)
+                return fail(MG_E_ARG, "%s: start state of image %d (%d) must be in [0, n_states = %d)", who, b, con->start_host[b], con->n_states);
+        if (m->dbg_forced)
+            return fail(MG_E_UNSUPPORTED, "%s: a constraint and forced ids (mg_debug_decode_capture) are not supported together", who);
+    }
     if (num_beams < 1 || num_beams > 8) return fail(MG_E_UNSUPPORTED, "%s: num_beams must be in [1, 8]", who);
     // the decode-step projections keep all live rows of a workgroup's feature slice in registers: at most 8 row tiles
     if ((long)B * num_beams > 256)
@@ -1496,7 +1522,8 @@ static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
     if (!e1 && m->e1m) M_e1 = m->e1_M;            // attached OCSR branch: mg_encode evaluates it (same workspace layout as with precomputed tokens)
     if (samp) carve(m, (char*)ws, B, L, NS, max_length, 0, M_e1, &w, 1);
     else carve(m, (char*)ws, B, L, K, max_length, 0, M_e1, &w);
-    const size_t ws_need = w.total + (prompt ? prompt_ws_bytes(B) : 0);      // the prompt lengths [B] follow the unprompted layout
+    const size_t con_off = w.total + (prompt ? prompt_ws_bytes(B) : 0);      // the prompt lengths [B] follow the unprompted layout,
+    const size_t ws_need = con_off + (con ? con_ws_bytes(B * K * NS, m->V) : 0);      // the constraint's states, class row and counter follow the lengths
     if (ws_need > ws_bytes) return fail(MG_E_WORKSPACE, "%s: workspace too small (%zu < %zu)", who, ws_bytes, ws_need);
     if (m->phase_on) mg_event_record(m->phase_ev[0], st);
     int rc = mg_encode(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, e1, M_in, B, L, nullptr, nullptr);
@@ -1517,6 +1544,21 @@ static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
         int* len_dev = (int*)((char*)ws + w.total);
         mg_memcpy_async(len_dev, m->prompt_len_host.data(), (size_t)B * sizeof(int32_t), st);
         dp.ids = prompt->ids; dp.len = len_dev; dp.ld = prompt->ld; dp.group = NS; dp.bad = counters + 3;
+    }
+    DecConstraint dcon{};
+    int con_empty_host = 0;
+    if (con) {         // every call starts from the images' start states; the class row is copied beside them, padded with class 0 (never read as a token)
+        m->con_start_host.resize(R);
+        for (int r = 0; r < R; ++r) m->con_start_host[r] = con->start_host[r / (K * NS)];
+        char* base = (char*)ws + con_off;
+        int* state_dev = (int*)base;
+        uint16_t* cls_dev = (uint16_t*)(base + con_state_bytes(R));
+        int* empty_dev = (int*)(base + con_state_bytes(R) + con_cls_bytes(m->V));
+        mg_memcpy_async(state_dev, m->con_start_host.data(), (size_t)R * sizeof(int32_t), st);
+        mg_memset_async(cls_dev, 0, con_cls_bytes(m->V), st);
+        mg_memcpy_async(cls_dev, con->cls, (size_t)m->V * sizeof(uint16_t), st);
+        mg_memset_async(empty_dev, 0, sizeof(int), st);
+        dcon = DecConstraint{cls_dev, con->table, con->n_states, con->n_classes, state_dev, empty_dev};
     }
     if (K == 1) {
         MG_LAUNCH(fill_ids_kernel, dim3(R), dim3(64), 0, st, db.next_ids, out_ids, db.unfinished, counters, R, max_length, start, pad, dp, m->V);
@@ -1543,6 +1585,7 @@ static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
     }
     dc.samp = samp;
     dc.prompt = dp;
+    dc.con = dcon;
     if (samp && NS > 1) {              // (the ancestor table's buffer is free: a sampled call has no beams.  The live-row skip of the attention
                                        // launches is per ROW in both cross-attention forms, so the samples of an image finish independently)
         MG_LAUNCH(row_owner_kernel, dim3((R + 255) / 256), dim3(256), 0, st, db.anc, R, NS);
@@ -1550,7 +1593,8 @@ static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
     }
     // greedy batch calls run the fused tail (lm_head top-2 partials -> selection + next embedding in one launch); the parity
     // instrumentation needs the full logits / overrides the fed token, and d_model > 2048 would change the norm's summation order
-    const bool fused_tail = K == 1 && !samp && m->fused_tail && !m->dbg_logits && !m->dbg_forced && d <= 2048;
+    // (a constrained call runs the unfused tail, as sampled calls do: the mask is not part of the lm_head epilogue)
+    const bool fused_tail = K == 1 && !samp && !con && m->fused_tail && !m->dbg_logits && !m->dbg_forced && d <= 2048;
     if (fused_tail)
         embed_norm_rows(db.next_ids, m->at<uint16_t>(m->tok_emb), db.dh, m->at<float>(m->dec[0].ln0), db.dx_pk, db.xa, d + inner, 0, R, d, m->V,
                         counters + 3, m->c.layer_norm_epsilon, st);      // the start token; later steps: greedy_select_fused
@@ -1565,6 +1609,7 @@ static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
         key.M_e1 = M_e1; key.length_penalty = length_penalty; key.token_scores = dc.token_scores; key.num_return = NS;
         if (samp) { key.top_k = samp->top_k; key.temperature = samp->temperature; key.top_p = samp->top_p; key.seed = samp->seed; key.stream_ids = samp->stream_ids; }
         key.prompt_ids = dp.ids; key.prompt_len = dp.len; key.prompt_ld = dp.ld;
+        if (con) { key.con_cls = con->cls; key.con_table = con->table; key.con_states = con->n_states; key.con_classes = con->n_classes; }
         graphed = m->step_graph.ensure(key, st, who, [&] { decode_step(0, counters + 2, false); });
     }
     m->graph_active = graphed;
@@ -1610,6 +1655,7 @@ static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
     mg_memcpy_async(host_flag, counters, sizeof host_flag, st);
     int beam_cols = 0;
     if (K > 1) mg_memcpy_async(&beam_cols, counters + 4, sizeof(int), st);
+    if (con) mg_memcpy_async(&con_empty_host, dcon.empty, sizeof(int), st);
     mg_stream_sync(st);
     rc = check_launch(who);
     if (rc != MG_OK) return rc;
@@ -1626,6 +1672,8 @@ static int generate_impl(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
     if (host_flag[3] != 0) return fail(MG_E_INPUT, "%s: %d token ids outside [0, vocab)", who, host_flag[3]);      // (encoder ids and prompt ids)
     if (K == 1) *out_cols_host = 1 + (host_flag[1] >= 0 ? host_flag[1] + 1 : steps_done);
     else *out_cols_host = beam_cols;
+    if (con_empty_host != 0)      // (the outputs are complete: such a row holds EOS where its allowed set was empty)
+        return fail(MG_E_INPUT, "%s: %d rows reached a state that allows no token (an EOS-only state below min_length; or no allowed token had a finite logit)", who, con_empty_host);
     return MG_OK;
 }
 
@@ -1669,6 +1717,32 @@ int mg_generate_prompted(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
     }
     return generate_impl(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, e1, M_e1, B, L, num_beams, max_length, min_length,
                          length_penalty, early_stopping, out_ids, out_cols_host, out_scores, step_top2, opts, nullptr, "mg_generate_prompted", prompt);
+}
+
+int mg_constrained_workspace_bytes(const mg_model* m, int B, int L, int rows_per_image, int max_length, int M_e1, int sampled, size_t* out_bytes) {
+    size_t base = 0;
+    const int rc = mg_prompted_workspace_bytes(m, B, L, rows_per_image, max_length, M_e1, sampled, &base);
+    if (rc != MG_OK) return rc;
+    *out_bytes = base + con_ws_bytes(B * rows_per_image, m->V);
+    return MG_OK;
+}
+
+int mg_generate_constrained(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
+                            const uint8_t* attention_mask, const float* pixel_values, const float* e1, int M_e1, int B, int L, int num_beams,
+                            int max_length, int min_length, float length_penalty, int early_stopping, int64_t* out_ids, int* out_cols_host,
+                            float* out_scores, float* step_top2, const mg_gen_opts* opts, const mg_sample_opts* samp,
+                            const mg_decoder_prompt* prompt, const mg_constraint* constraint) {
+    if (!constraint)
+        return mg_generate_prompted(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, e1, M_e1, B, L, num_beams, max_length,
+                                    min_length, length_penalty, early_stopping, out_ids, out_cols_host, out_scores, step_top2, opts, samp, prompt);
+    if (samp) {
+        if (num_beams != 1) return fail(MG_E_ARG, "mg_generate_constrained: a sampled call takes num_beams = 1 (got %d)", num_beams);
+        return generate_impl(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, e1, M_e1, B, L, 1, max_length, min_length, 1.0f,
+                             0, out_ids, out_cols_host, nullptr, step_top2, nullptr, samp, "mg_generate_constrained", prompt, constraint);
+    }
+    return generate_impl(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, e1, M_e1, B, L, num_beams, max_length, min_length,
+                         length_penalty, early_stopping, out_ids, out_cols_host, out_scores, step_top2, opts, nullptr, "mg_generate_constrained",
+                         prompt, constraint);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

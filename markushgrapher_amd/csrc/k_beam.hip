@@ -77,7 +77,8 @@ static BeamPtrs beam_ptrs(void* state, int B, int K, int max_len) {
 // Decoder prompt (pr.ids non-null): the K rows of image b hold its prompt in columns [0, len[b]) of both sequence arrays, as stock starts
 // them (utils.py:3326-3327); the running histories of the forced columns hold the image's beam-0 row and log-probability 0.
 __global__ __launch_bounds__(256) void beam_init_kernel(BeamPtrs p, int B, int K, int max_len, int fill, int start, int64_t* next_ids,
-                                                   int* anc, int T_cap, int* counters, DecPrompt pr, int V) {
+                                                   int* anc, int T_cap, int* counters, DecPrompt pr, int V, int* con_state,
+                                                   const int* con_start) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const int R = B * K;
     const int plen = pr.ids ? pr.len[b] : 0;
@@ -110,6 +111,7 @@ __global__ __launch_bounds__(256) void beam_init_kernel(BeamPtrs p, int B, int K
             if (first < 0 || first >= (int64_t)V) first = 0;
         }
         next_ids[b * K + i] = first;
+        if (con_state) con_state[b * K + i] = con_start[b];      // constraint: every row starts from its image's state
     }
     for (int i = tid; i < T_cap * K; i += 256) {   // identity ancestor table for this image's rows
         const int j = i / K, k = i - j * K;
@@ -121,10 +123,11 @@ __global__ __launch_bounds__(256) void beam_init_kernel(BeamPtrs p, int B, int K
     }
 }
 void beam_init(void* state, int B, int K, int max_len, int pad, int eos, int start, int64_t* next_ids, int* anc, int T_cap,
-               int* counters, mgStream_t stream, const DecPrompt* prompt, int V) {
+               int* counters, mgStream_t stream, const DecPrompt* prompt, int V, int* con_state, const int* con_start) {
     const BeamPtrs p = beam_ptrs(state, B, K, max_len);
     const DecPrompt pr = prompt ? *prompt : DecPrompt{};
-    MG_LAUNCH(beam_init_kernel, dim3(B), dim3(256), 0, stream, p, B, K, max_len, pad ? pad : eos, start, next_ids, anc, T_cap, counters, pr, V);
+    MG_LAUNCH(beam_init_kernel, dim3(B), dim3(256), 0, stream, p, B, K, max_len, pad ? pad : eos, start, next_ids, anc, T_cap, counters, pr, V,
+              con_start ? con_state : (int*)nullptr, con_start);
 }
 
 MG_DEV bool cand_before(float v1, int i1, float v2, int i2) { return v1 > v2 || (v1 == v2 && i1 < i2); }
@@ -153,9 +156,13 @@ MG_DEV float block_sum16(float v, float* red, int tid) {
     __syncthreads();
     return r;
 }
+// CON (batch form, DecConstraint in mg_kernels.h): the log-softmax stays over the raw logits; a token the row's state does not allow gets
+// the log-probability -inf on the line where MinLength's EOS does (stock's order: log_softmax, then the processors), in the in-register
+// branch, in the streaming branch and in the recomputation for the chosen candidate.  CON = false is the kernel as it was.
+template <bool CON>
 __global__ __launch_bounds__(BT_THREADS) void beam_row_topk_kernel(BeamPtrs p, const float* logits, int ldl, int V, int K, int cur_len_arg,
                                                               int eos, int min_len, const int* counters, const int* tdev, BeamSlots bs,
-                                                              DecPrompt pr) {
+                                                              DecPrompt pr, DecConstraint con) {
     // queue form (bs.pos): every image slot is at its own length, idle slots are skipped; batch form: one length, the batch's
     // continue flag
     if (bs.pos ? bs.live[blockIdx.x] == 0 : counters[0] == 0) return;
@@ -169,6 +176,13 @@ __global__ __launch_bounds__(BT_THREADS) void beam_row_topk_kernel(BeamPtrs p, c
     const bool no_eos = cur_len < min_len;
     const float* lg = logits + (size_t)row * ldl;
     const bool in_regs = V <= BT_THREADS * BT_NPT;
+    const int* trow = (const int*)(smem + 256);      // CON: [n_classes] the table row of this row's state, -1: not allowed
+    if (CON) {
+        const int* src = con.table + (size_t)con.state[row] * con.n_classes;
+        int* dst = (int*)(smem + 256);
+        for (int c = tid; c < con.n_classes; c += BT_THREADS) dst[c] = src[c];
+        __syncthreads();
+    }
     float x[BT_NPT];
     float mx = -3.0e38f;
     if (in_regs) {
@@ -197,6 +211,7 @@ __global__ __launch_bounds__(BT_THREADS) void beam_row_topk_kernel(BeamPtrs p, c
             const int v = tid + j * BT_THREADS;
             float lp = (x[j] - mx) - lse;
             if (no_eos && v == eos) lp = -INFINITY;
+            if (CON && v < V && trow[con.cls[v]] < 0) lp = -INFINITY;
             x[j] = v < V ? lp + rs : -INFINITY;
         }
     }
@@ -217,6 +232,7 @@ __global__ __launch_bounds__(BT_THREADS) void beam_row_topk_kernel(BeamPtrs p, c
             for (int v = tid; v < V; v += BT_THREADS) {
                 float lp = (lg[v] - mx) - lse;
                 if (no_eos && v == eos) lp = -INFINITY;
+                if (CON && trow[con.cls[v]] < 0) lp = -INFINITY;
                 const float val = lp + rs;
                 const int idx = k * V + v;
                 if (cand_before(lastv, lasti, val, idx) && cand_before(val, idx, bv, bi)) { bv = val; bi = idx; }
@@ -242,6 +258,7 @@ __global__ __launch_bounds__(BT_THREADS) void beam_row_topk_kernel(BeamPtrs p, c
             if (v >= 0 && v < V) {
                 lp = (lg[v] - mx) - lse;
                 if (no_eos && v == eos) lp = -INFINITY;
+                if (CON && trow[con.cls[v]] < 0) lp = -INFINITY;
             }
             p.rowlp[(size_t)row * keep + round] = lp;
         }
@@ -268,7 +285,8 @@ __global__ __launch_bounds__(128) void beam_merge_topk_kernel(BeamPtrs p, int K,
 // c.-g. bookkeeping for one image (K <= 8, 2K <= 16 candidates)
 __global__ __launch_bounds__(256) void beam_update_kernel(BeamPtrs p, int B, int K, int V, int max_len, int cur_len_arg, int eos,
                                                      float div_arg, const float* div_table, int early_stopping, int64_t* next_ids,
-                                                     int* beam_idx, const int* counters, const int* tdev, BeamSlots bs, DecPrompt pr) {
+                                                     int* beam_idx, const int* counters, const int* tdev, BeamSlots bs, DecPrompt pr,
+                                                     DecConstraint con) {
     if (bs.pos ? bs.live[blockIdx.x * K] == 0 : counters[0] == 0) return;
     const int cur_len = bs.pos ? bs.pos[blockIdx.x * K] + 1 : (tdev ? *tdev + 1 : cur_len_arg);
     // Decoder prompt: stock's decoder_prompt_len of THIS image (1 without a prompt).  A forced column appends the prompt's token (in the
@@ -373,6 +391,19 @@ __global__ __launch_bounds__(256) void beam_update_kernel(BeamPtrs p, int B, int
         }
     }
     __syncthreads();
+    // Constraint: running beam k continues candidate nxt[k] of parent src[nxt[k]] - its state is table[state[parent]][cls[token]], the sink
+    // where that entry is -1 (a -inf candidate was ranked).  The K rows are permuted: every old state is read before any new one is written.
+    if (con.cls) {
+        int ns = 0;
+        if (tid < K) {
+            const int c = nxt[tid], parent = src[c];
+            const int tok = p.topi[b * keep + c] - parent * V;
+            const int e = con.table[(size_t)con.state[b * K + parent] * con.n_classes + con.cls[tok]];
+            ns = e < 0 ? con.n_states - 1 : e;
+        }
+        __syncthreads();
+        if (tid < K) con.state[b * K + tid] = ns;
+    }
     // new finished set: gathered from the OLD sequences / candidates into temporaries, then copied back
     int64_t* tq = p.tmp_seq + (size_t)b * K * ml;
     int* ti = p.tmp_idx + (size_t)b * K * ml;
@@ -446,17 +477,22 @@ float beam_length_divisor(int cur_len, float length_penalty) { return (float)pow
 // filled on the host with beam_length_divisor so both forms use bit-identical values)
 void beam_step(void* state, const float* logits, int ldl, int V, int B, int K, int max_len, int cur_len, const int* tdev,
                const float* div_table, int eos, int min_len, float length_penalty, int early_stopping, int64_t* next_ids,
-               int* beam_idx, int* counters, mgStream_t stream, const BeamSlots* slots, const DecPrompt* prompt) {
+               int* beam_idx, int* counters, mgStream_t stream, const BeamSlots* slots, const DecPrompt* prompt, const DecConstraint* con) {
     const BeamPtrs p = beam_ptrs(state, B, K, max_len);
     const BeamSlots bs = slots ? *slots : BeamSlots{nullptr, nullptr};
     // a prompt belongs to the batch form and always takes its divisor from div_table (the prompt lengths live on the device)
     const DecPrompt pr = (prompt && !bs.pos) ? *prompt : DecPrompt{};
-    MG_LAUNCH(beam_row_topk_kernel, dim3(B * K), dim3(BT_THREADS), 256, stream, p, logits, ldl, V, K, cur_len, eos, min_len, (const int*)counters, tdev, bs,
-              pr);
+    const DecConstraint dc = (con && con->cls && !bs.pos) ? *con : DecConstraint{};      // (a constraint belongs to the batch form)
+    if (dc.cls)
+        MG_LAUNCH((beam_row_topk_kernel<true>), dim3(B * K), dim3(BT_THREADS), 256 + (size_t)dc.n_classes * sizeof(int), stream, p, logits, ldl, V, K,
+                  cur_len, eos, min_len, (const int*)counters, tdev, bs, pr, dc);
+    else
+        MG_LAUNCH((beam_row_topk_kernel<false>), dim3(B * K), dim3(BT_THREADS), 256, stream, p, logits, ldl, V, K, cur_len, eos, min_len,
+                  (const int*)counters, tdev, bs, pr, dc);
     MG_LAUNCH(beam_merge_topk_kernel, dim3(B), dim3(128), 1024, stream, p, K, (const int*)counters, bs, cur_len, tdev, pr);
     const float div = beam_length_divisor(cur_len, length_penalty);
     MG_LAUNCH(beam_update_kernel, dim3(B), dim3(256), 1024, stream, p, B, K, V, max_len, cur_len, eos, div,
-              (tdev || bs.pos || pr.ids) ? div_table : nullptr, early_stopping, next_ids, beam_idx, (const int*)counters, tdev, bs, pr);
+              (tdev || bs.pos || pr.ids) ? div_table : nullptr, early_stopping, next_ids, beam_idx, (const int*)counters, tdev, bs, pr, dc);
     if (!bs.pos) MG_LAUNCH(beam_flags_kernel, dim3(1), dim3(64), 0, stream, p, B, early_stopping, counters);
 }
 

@@ -374,11 +374,22 @@ MG_DEV void lse_merge(float& m, float& s, float m2, float s2) {
     else if (m2 > m) { s = s * expf(m - m2) + s2; m = m2; }
     else s += s2 * expf(m2 - m);
 }
+// CON (batch form, DecConstraint in mg_kernels.h): the table row of the row's state is staged in LDS once per launch (at most 16 KB); a
+// token lane loads the classes of its four tokens beside their logits, and a token whose entry is -1 is treated exactly as a suppressed
+// EOS: it cannot win and is left out of top2 and of the token-score normaliser.  CON = false is the kernel as it was.
+template <bool CON>
 __global__ __launch_bounds__(GS_THREADS) void greedy_select_kernel(ArgmaxArgs a) {
     MG_DYN_SMEM(smem);
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const float* lg = a.logits + (size_t)row * a.ldl;
     const bool stream = a.slots.pos != nullptr;
+    const int* trow = (const int*)(smem + 512);      // [n_classes] next state per class, -1: not allowed
+    if (CON) {
+        const int* src = a.con.table + (size_t)a.con.state[row] * a.con.n_classes;
+        int* dst = (int*)(smem + 512);
+        for (int c = tid; c < a.con.n_classes; c += GS_THREADS) dst[c] = src[c];
+        __syncthreads();
+    }
     const int pos = stream ? a.slots.pos[row] + 1 : (a.pos_dev ? *a.pos_dev + a.pos : a.pos);     // column written
     const bool no_eos = a.suppress_eos || pos < a.min_len;
     // stop tokens in registers (the argument block lives in device memory: no loads from it inside the scan)
@@ -393,10 +404,12 @@ __global__ __launch_bounds__(GS_THREADS) void greedy_select_kernel(ArgmaxArgs a)
     // 33 201 logits is 8.1 loads per thread; the kernel is latency-, not bandwidth-sized)
     for (int c0 = tid; c0 < nq; c0 += 4 * GS_THREADS) {
         float4 q[4];
+        uint2 k[4];                     // CON: the classes of the four tokens, 16 bits each
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int c = c0 + u * GS_THREADS;
             q[u] = c < nq ? *(const float4*)(lg + c * 4) : make_float4(-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f);
+            if (CON) k[u] = c < nq ? *(const uint2*)(a.con.cls + c * 4) : make_uint2(0u, 0u);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -407,6 +420,7 @@ __global__ __launch_bounds__(GS_THREADS) void greedy_select_kernel(ArgmaxArgs a)
                 const int i = c * 4 + j;
                 float v = vv[j];
                 if (i >= a.V || (no_eos && is_eos(i))) v = -3.0e38f;
+                if (CON && i < a.V && trow[((j < 2 ? k[u].x : k[u].y) >> ((j & 1) * 16)) & 0xffffu] < 0) v = -3.0e38f;
                 if (v > b1 || (v == b1 && i < i1)) { b2 = b1; b1 = v; i1 = i; }
                 else if (v > b2) b2 = v;
             }
@@ -434,10 +448,14 @@ __global__ __launch_bounds__(GS_THREADS) void greedy_select_kernel(ArgmaxArgs a)
         for (int c = tid; c < nq; c += GS_THREADS) {
             const float4 q = *(const float4*)(lg + c * 4);
             const float vv[4] = {q.x, q.y, q.z, q.w};
+            uint2 k = make_uint2(0u, 0u);
+            if (CON) k = *(const uint2*)(a.con.cls + c * 4);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int i = c * 4 + j;
-                se += (i < a.V && !(no_eos && is_eos(i))) ? expf(vv[j] - mx) : 0.f;
+                bool in = i < a.V && !(no_eos && is_eos(i));
+                if (CON && in) in = trow[((j < 2 ? k.x : k.y) >> ((j & 1) * 16)) & 0xffffu] >= 0;
+                se += in ? expf(vv[j] - mx) : 0.f;
             }
         }
         se = wave_sum(se);
@@ -470,9 +488,20 @@ __global__ __launch_bounds__(GS_THREADS) void greedy_select_kernel(ArgmaxArgs a)
         int64_t tok = unf ? (int64_t)i1 : (int64_t)a.pad;
         // decoder prompt: a forced column takes the prompt's token, scores 0 and leaves the row live (a row in its prompt has never finished)
         const bool forced = prompt_forced(a.prompt, row, pos, a.V, tok);
+        bool scored = unf && !forced;
+        if (CON && scored) {            // a live row in a free column advances its state with the token it emits
+            if (b1 == -3.0e38f) {       // nothing is allowed (MinLength included; or every allowed logit is -inf / NaN): EOS ends the row in the sink
+                tok = (int64_t)a.eos;
+                scored = false;
+                a.con.state[row] = a.con.n_states - 1;
+                atomicAdd(a.con.empty, 1);
+            } else {
+                a.con.state[row] = trow[a.con.cls[tok]];
+            }
+        }
         a.next_ids[row] = tok;
         if (pos < a.max_len) a.out_ids[(size_t)row * a.max_len + pos] = tok;
-        if (a.token_scores && pos < a.max_len) a.token_scores[(size_t)row * a.ts_ld + pos - 1] = (unf && !forced) ? -logf(se) : 0.f;
+        if (a.token_scores && pos < a.max_len) a.token_scores[(size_t)row * a.ts_ld + pos - 1] = scored ? -logf(se) : 0.f;
         const int still = forced ? 1 : (unf && !is_eos((int)tok));
         a.unfinished[row] = still;
         if (still) atomicAdd(a.n_unfinished, 1);
@@ -670,7 +699,10 @@ void greedy_select_fused(const ArgmaxArgs& a, mgStream_t stream) {
 }
 
 void greedy_select(const ArgmaxArgs& a, mgStream_t stream) {
-    MG_LAUNCH(greedy_select_kernel, dim3(a.rows), dim3(GS_THREADS), 512, stream, a);
+    if (a.con.cls)      // (batch form; the callers refuse a slot table and more than DEC_CON_MAX_CLASSES classes)
+        MG_LAUNCH((greedy_select_kernel<true>), dim3(a.rows), dim3(GS_THREADS), 512 + (size_t)a.con.n_classes * sizeof(int), stream, a);
+    else
+        MG_LAUNCH((greedy_select_kernel<false>), dim3(a.rows), dim3(GS_THREADS), 512, stream, a);
 }
 
 }  // namespace mg

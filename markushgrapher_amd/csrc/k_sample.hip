@@ -111,7 +111,9 @@ MG_DEV uint32_t ss_radix_select(const uint32_t (&keys)[NQ * 4], const uint32_t (
 
 // QUEUE: the continuous decoder's form (SampleArgs::slots, mg_kernels.h) - the row's column, output row and random stream are those of
 // the sequence in the slot (three wave-uniform scalars); everything that decides the token is the batch form's code.
-template <int NQ, int NT, bool QUEUE>
+// CON (batch form, DecConstraint in mg_kernels.h): the tokens the row's state does not allow become -inf where MinLength's EOS does, in
+// the registers that hold the row, before temperature, top-k, top-p and the draw; the draw's counter and stream are unchanged.
+template <int NQ, int NT, bool QUEUE, bool CON = false>
 __global__ __launch_bounds__(NT) void sample_select_kernel(SampleArgs a) {
     MG_DYN_SMEM(smem);
     u64* hist = (u64*)smem;                  // [256][SS_COPIES]
@@ -119,6 +121,7 @@ __global__ __launch_bounds__(NT) void sample_select_kernel(SampleArgs a) {
     u64* sel = wtot + 16;                    // [2] digit and running base of a radix pass
     float* rv = (float*)(sel + 2);           // [16][2]
     int* ri = (int*)(rv + 32);               // [16]
+    int* trow = ri + 16;                     // CON: [n_classes] the table row of the row's state
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int unf = a.unfinished[row];       // (queue form: 0 = idle slot, computed on stale inputs - nothing is written, nothing is drawn)
     // Queue form: both slot-table loads stay HERE, in front of the first barrier.  The lane that holds the draw later stores slots.pos[row]
@@ -145,10 +148,17 @@ __global__ __launch_bounds__(NT) void sample_select_kernel(SampleArgs a) {
         const int nq = (a.V + 3) >> 2;       // rows are padded to a multiple of 32 floats, so the last float4 is readable
         const int c0 = w * 64 * NQ + lane;
         float4 q[NQ];
+        uint2 kc[CON ? NQ : 1];              // CON: the classes of a load's four tokens, 16 bits each
 #pragma unroll
         for (int u = 0; u < NQ; ++u) {
             const int c = c0 + u * 64;
             q[u] = c < nq ? *(const float4*)(lg + c * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (CON) kc[u] = c < nq ? *(const uint2*)(a.con.cls + c * 4) : make_uint2(0u, 0u);
+        }
+        if (CON) {                           // (the branch is uniform over the workgroup: unf and forced are the row's)
+            const int* src = a.con.table + (size_t)a.con.state[row] * a.con.n_classes;
+            for (int c = tid; c < a.con.n_classes; c += NT) trow[c] = src[c];
+            __syncthreads();
         }
         uint32_t m[NQ * 4], keys[NQ * 4];     // the row is kept as (key, mass) pairs; a key gives its float back (ss_unkey)
         b1 = -3.0e38f; b2 = -3.0e38f;
@@ -160,7 +170,9 @@ __global__ __launch_bounds__(NT) void sample_select_kernel(SampleArgs a) {
             for (int j = 0; j < 4; ++j) {
                 const int i = (c0 + u * 64) * 4 + j;
                 // tokens past V and a suppressed EOS leave the distribution: -inf has mass 0 and sorts below every logit (-0 -> +0: one key per value)
-                const float x = (i >= a.V || (no_eos && i == a.eos)) ? ss_neg_inf() : vv[j] + 0.0f;
+                bool out = i >= a.V || (no_eos && i == a.eos);
+                if (CON && !out) out = trow[((j < 2 ? kc[u].x : kc[u].y) >> ((j & 1) * 16)) & 0xffffu] < 0;
+                const float x = out ? ss_neg_inf() : vv[j] + 0.0f;
                 keys[u * 4 + j] = ss_key(x);
                 if (x > b1 || (x == b1 && i < i1)) { b2 = b1; b1 = x; i1 = i; }
                 else if (x > b2) b2 = x;
@@ -184,6 +196,8 @@ __global__ __launch_bounds__(NT) void sample_select_kernel(SampleArgs a) {
         }
         // top-k: k clamped to the tokens in the distribution
         uint32_t kmin = 0;
+        // (CON: n_alive does not count the masked tokens.  A top_k above the allowed count then selects a -inf key as the k-th largest: every
+        // finite token survives and the -inf ones carry mass 0 - what the unconstrained kernel does on host-masked logits, bit for bit.)
         int n_alive = a.V - ((no_eos && a.eos >= 0 && a.eos < a.V) ? 1 : 0);
         if (a.top_k > 0 && a.top_k < n_alive) kmin = ss_radix_select<NQ, false, NT>(keys, m, hist, sel, 0u, (u64)(a.top_k - 1), tid);
         // top-p over the top-k survivors
@@ -225,6 +239,13 @@ __global__ __launch_bounds__(NT) void sample_select_kernel(SampleArgs a) {
         if (total == 0) {                    // no finite logit in the row (never with a model's logits): emit the arg-max slot, keep the protocol
             writer = tid == 0;
             tok = (int64_t)(i1 < a.V ? i1 : 0);
+            // CON: no mass at all counts as the empty allowed set - also when the allowed tokens' logits are all -inf or not finite, which a
+            // model's logits never are.  EOS ends the row in the sink, score 0.0, no draw
+            if (CON && tid == 0) {
+                tok = (int64_t)a.eos;
+                a.con.state[row] = a.con.n_states - 1;
+                atomicAdd(a.con.empty, 1);
+            }
         } else if (target >= before && target < before + mine) {      // wave-uniform: this wave holds the target
             u64 t = target - before;
             bool found = false;
@@ -258,6 +279,7 @@ __global__ __launch_bounds__(NT) void sample_select_kernel(SampleArgs a) {
                     }
                     excl += ms[j];
                 }
+                if (CON) a.con.state[row] = trow[a.con.cls[tok]];      // the row's state advances with the drawn token
             }
         }
     }
@@ -311,6 +333,13 @@ void sample_select(const SampleArgs& a, mgStream_t stream) {
         if (a.V <= 4096) MG_LAUNCH((sample_select_kernel<1, 1024, true>), dim3(a.rows), dim3(1024), lds, stream, a);
         else if (a.V <= 4096 * 3) MG_LAUNCH((sample_select_kernel<3, 1024, true>), dim3(a.rows), dim3(1024), lds, stream, a);
         else MG_LAUNCH((sample_select_kernel<18, 512, true>), dim3(a.rows), dim3(512), lds, stream, a);
+        return;
+    }
+    if (a.con.cls) {
+        const size_t ldc = lds + (size_t)a.con.n_classes * sizeof(int);
+        if (a.V <= 4096) MG_LAUNCH((sample_select_kernel<1, 1024, false, true>), dim3(a.rows), dim3(1024), ldc, stream, a);
+        else if (a.V <= 4096 * 3) MG_LAUNCH((sample_select_kernel<3, 1024, false, true>), dim3(a.rows), dim3(1024), ldc, stream, a);
+        else MG_LAUNCH((sample_select_kernel<18, 512, false, true>), dim3(a.rows), dim3(512), ldc, stream, a);
         return;
     }
     if (a.V <= 4096) MG_LAUNCH((sample_select_kernel<1, 1024, false>), dim3(a.rows), dim3(1024), lds, stream, a);

@@ -435,6 +435,19 @@ MG_DEV bool prompt_forced(const DecPrompt& p, int row, int col, int V, int64_t& 
     tok = t;
     return true;
 }
+// Constraint of the batch decode loops (mg_generate_constrained): a finite automaton over token classes.  Row r is in state[r]; a token
+// t is allowed there iff table[state[r]][cls[t]] >= 0, and that entry is the row's next state.  The selection kernels mask the
+// disallowed tokens exactly as MinLength masks EOS and advance the state with the token they emit; a forced prompt column and a finished
+// row leave the state alone.  The last state is the sink (EOS only).  A live row whose allowed set is empty (MinLength included) emits
+// EOS, ends, moves to the sink, scores 0.0, draws nothing and adds one to *empty.  cls == null: no constraint.
+struct DecConstraint {
+    const uint16_t* cls;     // [ldl] class of every token, padded to the logits' row stride (read with the logits' vector pattern)
+    const int* table;        // [n_states][n_classes] next state, -1: not allowed
+    int n_states, n_classes; // n_classes <= DEC_CON_MAX_CLASSES: a state's table row is staged in LDS
+    int* state;              // [rows]
+    int* empty;              // [1] counter
+};
+constexpr int DEC_CON_MAX_CLASSES = 4096;
 struct ArgmaxArgs {
     const float* logits;     // [rows][ldl]
     int rows, V, ldl;
@@ -473,6 +486,7 @@ struct ArgmaxArgs {
     float* token_scores;
     int ts_ld;               // columns per row of token_scores (max_len - 1)
     DecPrompt prompt;        // batch forms only (slots.pos == null); ids null: none
+    DecConstraint con;       // batch form of greedy_select only (no slot table, no fused tail); cls null: none
 };
 void greedy_select(const ArgmaxArgs& a, mgStream_t stream);
 void greedy_select_fused(const ArgmaxArgs& a, mgStream_t stream);
@@ -503,6 +517,7 @@ struct SampleArgs {
     int ts_ld;
     SlotTable slots;         // continuous decoding (slots.pos == null: batch form)
     DecPrompt prompt;        // batch form only; a forced row makes no draw
+    DecConstraint con;       // batch form only; cls null: none.  The mask is applied where MinLength's is: before temperature, top-k, top-p
 };
 bool sample_select_supported(int V);     // the row is held in registers: V <= 36 864
 void sample_select(const SampleArgs& a, mgStream_t stream);
@@ -530,11 +545,13 @@ size_t beam_state_bytes(int B, int K, int max_len);
 // prompt (nullable; batch form, one owner per image, group ignored): the K rows of image b start holding its prompt (stock writes
 // input_ids into running_sequences and sequences, utils.py:3326-3327), V bounds its ids
 void beam_init(void* state, int B, int K, int max_len, int pad, int eos, int start, int64_t* next_ids, int* anc, int T_cap,
-               int* counters, mgStream_t stream, const DecPrompt* prompt = nullptr, int V = 0);
+               int* counters, mgStream_t stream, const DecPrompt* prompt = nullptr, int V = 0, int* con_state = nullptr,
+               const int* con_start = nullptr);      // con_start [B] (device, nullable): con_state[b * K + k] = con_start[b]
 float beam_length_divisor(int cur_len, float length_penalty);
 void beam_step(void* state, const float* logits, int ldl, int V, int B, int K, int max_len, int cur_len, const int* tdev,
                const float* div_table, int eos, int min_len, float length_penalty, int early_stopping, int64_t* next_ids,
-               int* beam_idx, int* counters, mgStream_t stream, const BeamSlots* slots = nullptr, const DecPrompt* prompt = nullptr);
+               int* beam_idx, int* counters, mgStream_t stream, const BeamSlots* slots = nullptr, const DecPrompt* prompt = nullptr,
+               const DecConstraint* con = nullptr);      // con (batch form): the row top-k masks, the update reorders and advances the K states
 // n-best output of an image's finished hypotheses (best first).  Hypothesis h < num_return of image i is output row i * num_return + h:
 // out_ids [rows][max_len], scores [rows] (sequence scores), and, nullable, beam_indices [rows][max_len - 1] (stock semantics: the flat row
 // image * K + beam each token was chosen from, -1 past the hypothesis' length) and token_scores [rows][max_len - 1] (the processed

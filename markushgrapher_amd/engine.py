@@ -44,6 +44,17 @@ class MgDecoderPrompt(C.Structure):
     _fields_ = [("ids", C.c_void_p), ("len_host", C.c_void_p), ("ld", C.c_int)]
 
 
+class MgConstraint(C.Structure):
+    """include/mgrapher.h mg_constraint: cls [vocab] u16 and table [n_states][n_classes] i32 on the device, the start states [B] on the host."""
+    _fields_ = [("cls", C.c_void_p), ("table", C.c_void_p), ("n_states", C.c_int), ("n_classes", C.c_int), ("start_host", C.c_void_p)]
+
+
+class MgkConstraint(C.Structure):
+    """include/mgrapher.h mgk_constraint (the operator entries mgk_*_constrained): everything on the device, cls padded to the logits' stride."""
+    _fields_ = [("cls", C.c_void_p), ("table", C.c_void_p), ("n_states", C.c_int), ("n_classes", C.c_int), ("state", C.c_void_p),
+                ("empty", C.c_void_p)]
+
+
 class TorchMem:
     """Device memory carried by torch tensors on one GPU."""
 
@@ -161,6 +172,8 @@ class Engine:
                                           C.POINTER(MgSampleOpts)]
         L.mg_prompted_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         L.mg_generate_prompted.argtypes = L.mg_generate_scored.argtypes + [C.POINTER(MgSampleOpts), C.POINTER(MgDecoderPrompt)]
+        L.mg_constrained_workspace_bytes.argtypes = L.mg_prompted_workspace_bytes.argtypes
+        L.mg_generate_constrained.argtypes = L.mg_generate_prompted.argtypes + [C.POINTER(MgConstraint)]
         L.mg_stream_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         L.mg_generate_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + \
                                         [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.POINTER(C.c_long)]
@@ -299,12 +312,15 @@ class Engine:
         k = self.lib.mg_debug_bucket_table(self.model, which, out, n)
         return np.array(out[:k], dtype=np.int32)
 
-    def workspace(self, B, L, num_beams, max_length, T, M_e1=0, sampled=False, prompted=False):
+    def workspace(self, B, L, num_beams, max_length, T, M_e1=0, sampled=False, prompted=False, constrained=False):
         """The context's workspace, grown to what the call needs.  sampled: num_beams is the samples per image of a generate_sampled call
         (mg_sampled_workspace_bytes: its rows choose the cross-attention form as greedy rows).  prompted: a call with a decoder prompt
-        (mg_prompted_workspace_bytes: the unprompted size plus the prompt lengths)."""
+        (mg_prompted_workspace_bytes: the unprompted size plus the prompt lengths).  constrained: a call with a constraint, with or without
+        a prompt (mg_constrained_workspace_bytes: the prompted size plus the rows' states, the padded class row and the counter)."""
         need = C.c_size_t()
-        if prompted:
+        if constrained:
+            self._chk(self.lib.mg_constrained_workspace_bytes(self.model, B, L, num_beams, max_length, M_e1, 1 if sampled else 0, C.byref(need)))
+        elif prompted:
             self._chk(self.lib.mg_prompted_workspace_bytes(self.model, B, L, num_beams, max_length, M_e1, 1 if sampled else 0, C.byref(need)))
         elif sampled:
             self._chk(self.lib.mg_sampled_workspace_bytes(self.model, B, L, num_beams, max_length, M_e1, C.byref(need)))
@@ -516,15 +532,53 @@ class Engine:
         self._prompt_keep = (buf, lens)
         return MgDecoderPrompt(self.mem.ptr(buf).value, lens.ctypes.data, P)
 
+    def _constraint(self, constraint, constraint_start, B):
+        """TokenAutomaton (+ constraint_start [B], default state 0) -> MgConstraint, or None without a constraint.  The tables live in device
+        buffers kept per (vocab, states, classes): an automaton is uploaded once, and another one of the same sizes is written IN PLACE, so
+        the captured decode step, whose key holds the tables' addresses and sizes, is replayed.  The entries' ranges were checked by
+        TokenAutomaton's constructor; the library checks the sizes and the start states (MG_E_ARG)."""
+        if constraint is None:
+            if constraint_start is not None:
+                raise ValueError("constraint_start needs constraint")
+            return None
+        from .constraint import TokenAutomaton
+        if not isinstance(constraint, TokenAutomaton):
+            raise TypeError("constraint must be a markushgrapher_amd.constraint.TokenAutomaton")
+        if constraint.vocab != self.shape.vocab_size:
+            raise ValueError(f"the constraint covers {constraint.vocab} tokens, the model's vocabulary has {self.shape.vocab_size}")
+        if constraint_start is None:
+            starts = np.zeros((B,), np.int32)
+        else:
+            if hasattr(constraint_start, "detach"):
+                constraint_start = constraint_start.detach().cpu().numpy()
+            starts = np.ascontiguousarray(np.asarray(constraint_start).reshape(-1).astype(np.int32))
+            if starts.shape[0] != B:
+                raise ValueError(f"constraint_start must hold B = {B} states, got {starts.shape[0]}")
+        cache = self.__dict__.setdefault("_con_buf", {})
+        key = (constraint.vocab, constraint.n_states, constraint.n_classes)
+        if key not in cache:
+            if len(cache) > 8:
+                cache.clear()
+            cache[key] = {"cls": self.mem.zeros((key[0],), np.uint16), "table": self.mem.zeros(key[1:], np.int32), "held": None}
+        c = cache[key]
+        if c["held"] is not constraint:
+            c["cls"][...] = self.mem.asarray(constraint.cls, np.uint16)
+            c["table"][...] = self.mem.asarray(constraint.table, np.int32)
+            c["held"] = constraint
+        self._con_keep = (c, starts)
+        return MgConstraint(self.mem.ptr(c["cls"]).value, self.mem.ptr(c["table"]).value, key[1], key[2], starts.ctypes.data)
+
     def generate_sampled(self, input_ids, bbox, attention_mask, pixel_values, max_length=512, min_length=0, temperature=1.0, top_k=0,
                          top_p=1.0, seed=0, num_return=1, stream_ids=None, return_scores=False, return_top2=False, e1=None,
-                         decoder_prompt=None, decoder_prompt_len=None):
+                         decoder_prompt=None, decoder_prompt_len=None, constraint=None, constraint_start=None):
         """Sampled decoding (include/mgrapher.h mg_generate_sampled): temperature, top-k (0 = off), top-p (1 = off) in stock's order, one
         Philox4x32-10 draw per live row and step at counter (stream id, column) under the key `seed`.  -> (ids [B * num_return, cols],
         cols, token_scores [B * num_return, cols - 1] or None[, top2]): row b * num_return + j is sample j of image b.  stream_ids
         [B * num_return] (default: the row index) name the rows' random streams: a row's draws depend on (seed, stream id, column) and its own
         logits only.  decoder_prompt [B, P] / decoder_prompt_len [B]: image b's samples all start with its prompt (mg_generate_prompted);
-        forced columns draw nothing and score 0.0."""
+        forced columns draw nothing and score 0.0.  constraint (a TokenAutomaton) / constraint_start [B] (default state 0): the tokens a
+        row's state does not allow leave its distribution before temperature, top-k and top-p (mg_generate_constrained); all samples of
+        image b start from constraint_start[b], the state at its first free column (after a prompt: automaton.run(0, prompt[1:len]))."""
         ids, bb, am, pv, B, L = self._inputs(input_ids, bbox, attention_mask, pixel_values)
         nr = int(num_return)
         if nr < 1:
@@ -540,7 +594,8 @@ class Engine:
             raise MgError(f"generate_sampled: B * num_return = {R} live sequences exceeds the supported {self.MAX_LIVE_ROWS}; split the batch")
         e1t, M = self._e1(e1, B)
         prompt = self._prompt(decoder_prompt, decoder_prompt_len, B)
-        ws, nb = self.workspace(B, L, nr, max_length, 0, M, sampled=True, prompted=prompt is not None)
+        con = self._constraint(constraint, constraint_start, B)
+        ws, nb = self.workspace(B, L, nr, max_length, 0, M, sampled=True, prompted=prompt is not None, constrained=con is not None)
         # persistent output / stream-id buffers: the captured decode step holds their addresses (see generate)
         cache = self._samp_out
         okey = (R, max_length)
@@ -562,7 +617,14 @@ class Engine:
                             self.mem.ptr(sid).value if sid is not None else None, nr,
                             self.mem.ptr(c["ts"]).value if return_scores else None)
         cols = C.c_int(0)
-        if prompt is not None:
+        if con is not None:
+            self._chk(self.lib.mg_generate_constrained(
+                self.model, self.mem.stream(), self.mem.ptr(ws), nb, self.mem.ptr(ids), self.mem.ptr(bb),
+                self.mem.ptr(am) if am is not None else None, self.mem.ptr(pv), self.mem.ptr(e1t) if e1t is not None else None, M, B, L,
+                1, max_length, min_length, C.c_float(1.0), 0, self.mem.ptr(c["ids"]), C.byref(cols), None,
+                self.mem.ptr(top2) if top2 is not None else None, None, C.byref(opts), C.byref(prompt) if prompt is not None else None,
+                C.byref(con)))
+        elif prompt is not None:
             self._chk(self.lib.mg_generate_prompted(
                 self.model, self.mem.stream(), self.mem.ptr(ws), nb, self.mem.ptr(ids), self.mem.ptr(bb),
                 self.mem.ptr(am) if am is not None else None, self.mem.ptr(pv), self.mem.ptr(e1t) if e1t is not None else None, M, B, L,
@@ -703,14 +765,19 @@ class Engine:
 
     def generate(self, input_ids, bbox, attention_mask, pixel_values, num_beams=1, max_length=512, min_length=0,
                  length_penalty=1.0, early_stopping=False, return_top2=False, e1=None, num_return=1, return_scores=False,
-                 decoder_prompt=None, decoder_prompt_len=None):
+                 decoder_prompt=None, decoder_prompt_len=None, constraint=None, constraint_start=None):
         """-> (ids [B, cols], scores [B] (beam: sequences_scores), top2 or None).  num_return (beam: 1 .. num_beams): the n-best list,
         ids [B * num_return, cols] and scores [B * num_return], hypotheses of an image consecutive, best first; cols = the longest
         returned hypothesis'.  return_scores: a fourth item {"token_scores": [rows, cols - 1], "beam_indices": [rows, cols - 1] (beam) or
         None} - include/mgrapher.h mg_generate_scored.
         decoder_prompt [B, P] int64 / decoder_prompt_len [B] (default all P): image b's rows start with decoder_prompt[b, :len[b]] and
         decode freely from there (include/mgrapher.h mg_generate_prompted); the returned ids include the prompt, token_scores are 0.0 in
-        its columns."""
+        its columns.
+        constraint (a TokenAutomaton) / constraint_start [B] (default state 0): greedy decoding under the automaton
+        (mg_generate_constrained) - a token the row's state does not allow cannot be chosen and is left out of top2 and of the token
+        scores' normaliser; constraint_start[b] is image b's state at its first free column (after a prompt: automaton.run(0,
+        prompt[1:len])).  A greedy call runs the unfused selection tail.  Beam search: the mask sets a candidate's log-probability to -inf
+        after the log-softmax over the raw logits, as stock's processors do; the K rows' states follow the beams."""
         ids, bb, am, pv, B, L = self._inputs(input_ids, bbox, attention_mask, pixel_values)
         nr = int(num_return)
         if not 1 <= nr <= num_beams:
@@ -720,7 +787,9 @@ class Engine:
             raise MgError(f"generate: B * num_beams = {B * num_beams} live sequences exceeds the supported "
                           f"{self.MAX_LIVE_ROWS}; split the batch")
         prompt = self._prompt(decoder_prompt, decoder_prompt_len, B)
-        ws, nb = self.workspace(B, L, num_beams, max_length, 0, M, prompted=prompt is not None)
+        con = self._constraint(constraint, constraint_start, B)
+        ws, nb = self.workspace(B, L, num_beams, max_length, 0, M, prompted=prompt is not None, constrained=con is not None)
+        p_ref = C.byref(prompt) if prompt is not None else None
         # the id buffer is persistent per (B, max_length): the captured decode-step graph holds its address, so a stable
         # buffer lets later calls replay the graph instead of re-capturing; callers get a copy
         okey = (B * nr, max_length)
@@ -736,7 +805,9 @@ class Engine:
                 num_beams, max_length, min_length, C.c_float(length_penalty), 1 if early_stopping is True else 0,
                 self.mem.ptr(out), C.byref(cols), self.mem.ptr(scores), self.mem.ptr(top2) if top2 is not None else None)
         if nr == 1 and not return_scores:
-            if prompt is not None:
+            if con is not None:
+                self._chk(self.lib.mg_generate_constrained(*args, None, None, p_ref, C.byref(con)))
+            elif prompt is not None:
                 self._chk(self.lib.mg_generate_prompted(*args, None, None, C.byref(prompt)))
             else:
                 self._chk(self.lib.mg_generate(*args))
@@ -747,7 +818,9 @@ class Engine:
         opts.seq_scores = self.mem.ptr(scores).value if beam else None
         if not return_scores:
             opts.token_scores = opts.beam_indices = None
-        if prompt is not None:
+        if con is not None:
+            self._chk(self.lib.mg_generate_constrained(*args, C.byref(opts), None, p_ref, C.byref(con)))
+        elif prompt is not None:
             self._chk(self.lib.mg_generate_prompted(*args, C.byref(opts), None, C.byref(prompt)))
         else:
             self._chk(self.lib.mg_generate_scored(*args, C.byref(opts)))

@@ -543,8 +543,71 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
                                  "raise `max_length` or pass `max_new_tokens`")
         return dec, lens, P, max_length, int(min_length)
 
+    _CONSTRAINT_KEYS = ("constraint", "suppress_tokens", "begin_suppress_tokens", "bad_words_ids", "prefix_allowed_tokens_fn",
+                        "repetition_penalty", "no_repeat_ngram_size")
+
+    @staticmethod
+    def _refuse_not_built(kw):
+        """the knobs of this family that are not masks, and the callback that cannot run under the captured step: refused, never dropped"""
+        if kw.pop("prefix_allowed_tokens_fn", None) is not None:
+            raise ValueError("`prefix_allowed_tokens_fn` is a Python callback and cannot run under the captured decode step; compile the rule "
+                             "to a token automaton and pass `constraint=` (markushgrapher_amd.constraint)")
+        rp = kw.pop("repetition_penalty", None)
+        if rp is not None and float(rp) != 1.0:
+            raise ValueError(f"`repetition_penalty` is not built (it changes logit values; got {rp}): only 1.0 is accepted")
+        ng = kw.pop("no_repeat_ngram_size", None)
+        if ng is not None and int(ng) > 0:
+            raise ValueError(f"`no_repeat_ngram_size` is not built (it needs unbounded history; got {ng}): only 0 is accepted")
+
+    def _constraint(self, kw, dec, dec_len, B):
+        """constraint= (a TokenAutomaton), suppress_tokens=, begin_suppress_tokens=, bad_words_ids= -> (automaton or None, start states [B]).
+        All given ones are combined into one product automaton.  With a decoder prompt, image b starts in the state its prompt leaves
+        (TokenAutomaton.run_forced over prompt[1:len]: a banned token inside a prompt is accepted, as in stock, and only moves the state);
+        begin_suppress_tokens applies at the first free column, so its component starts after the prompt."""
+        from . import constraint as K
+        self._refuse_not_built(kw)
+        user, sup = kw.pop("constraint", None), kw.pop("suppress_tokens", None)
+        beg, bad = kw.pop("begin_suppress_tokens", None), kw.pop("bad_words_ids", None)
+        V, eos = int(self.config.vocab_size), int(self.config.eos_token_id)
+        comps = []                                               # (automaton, it follows the prompt)
+        if user is not None:
+            if not isinstance(user, K.TokenAutomaton):
+                raise ValueError("`constraint` must be a markushgrapher_amd.constraint.TokenAutomaton")
+            if user.vocab != V or user.eos != eos:
+                raise ValueError(f"`constraint` is over {user.vocab} tokens with EOS {user.eos}; the model has {V} and {eos}")
+            comps.append((user, True))
+        if sup is not None and len(sup):
+            comps.append((K.suppress(V, eos, sup), True))
+        if bad is not None and len(bad):
+            comps.append((K.bad_words(V, eos, bad), True))
+        if beg is not None and len(beg):
+            comps.append((K.begin_suppress(V, eos, beg), False))
+        if not comps:
+            return None, None
+        rows = [[] for _ in range(B)]
+        if dec is not None:
+            host = dec.detach().cpu().numpy()
+            rows = [host[b, 1:(host.shape[1] if dec_len is None else int(dec_len[b]))] for b in range(B)]
+        states = [tuple(a.run_forced(0, rows[b]) if follows else 0 for a, follows in comps) for b in range(B)]
+        if len(comps) == 1:
+            return comps[0][0], np.array([s[0] for s in states], np.int32)
+        aut, idx = K.product([a for a, _ in comps], starts=states)
+        return aut, np.asarray(idx, np.int32)
+
+    @staticmethod
+    def _mask_scores(sc, ids, aut, starts, first, group):
+        """output_scores under a constraint: -inf where the row's state does not allow the token, applied on the host from the automaton as
+        MinLength is; sc [steps, rows, V] (step t decides column t + 1), row r belongs to image r // group"""
+        seq = ids.detach().cpu().numpy() if hasattr(ids, "detach") else np.asarray(ids)
+        for r in range(sc.shape[1]):
+            st = int(starts[r // group])
+            for t in range(first, sc.shape[0]):
+                sc[t, r, torch.from_numpy(~aut.allowed_mask(st)).to(sc.device)] = -float("inf")
+                st = aut.step(st, seq[r, t + 1])
+        return sc
+
     def _generate_sampled(self, input_ids, bbox, pixel_values, attention_mask, num_beams, max_length, min_length, e1, num_return, as_dict,
-                          want_scores, want_logits, kw, prompt=(None, None, 1)):
+                          want_scores, want_logits, kw, prompt=(None, None, 1), con=(None, None)):
         """generate(do_sample=True): stock `_sample` with the temperature / top-k / top-p warpers, drawn on the device
         (include/mgrapher.h mg_generate_sampled).  temperature=1.0, top_k=None (generation_config.top_k if the model has one, else stock's
         default 50; 0 = off), top_p=1.0, num_return_sequences=1, seed=None, stream_ids=None.
@@ -563,7 +626,8 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
         max_length = int(max_length or self.config.max_length)
         attention_mask = self._default_mask(input_ids, attention_mask)
         skw = dict(max_length=max_length, min_length=int(min_length), temperature=temperature, top_k=int(top_k), top_p=top_p, seed=int(seed),
-                   num_return=num_return, stream_ids=stream_ids, e1=e1, decoder_prompt=prompt[0], decoder_prompt_len=prompt[1])
+                   num_return=num_return, stream_ids=stream_ids, e1=e1, decoder_prompt=prompt[0], decoder_prompt_len=prompt[1],
+                   constraint=con[0], constraint_start=con[1])
         first = prompt[2] - 1 if prompt[2] else 0      # output_scores / output_logits hold the free steps only, as stock's do
         if not as_dict:
             return eng.generate_sampled(input_ids, bbox, attention_mask, pixel_values, **skw)[0]
@@ -585,6 +649,8 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
                 sc = raw.clone()
                 for t in range(min(steps, max(0, int(min_length) - 1))):
                     sc[t, :, self.config.eos_token_id] = -float("inf")
+                if con[0] is not None:
+                    self._mask_scores(sc, ids, con[0], con[1], first, num_return)
                 out.scores = tuple(sc[t] / temperature for t in range(first, steps))
         return out
 
@@ -597,7 +663,11 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
         decoder_input_ids= [B, P] (with decoder_attention_mask= for prompts of different lengths): the answers start with the given tokens
         and the model writes the rest, in all three decode modes (include/mgrapher.h mg_generate_prompted; rules: _decoder_prompt).  The
         returned sequences include the prompt, token_scores are 0.0 in its columns, output_scores / output_logits hold the free steps only.
-        max_new_tokens= / min_new_tokens= count from the prompt's end (from the start token without one)."""
+        max_new_tokens= / min_new_tokens= count from the prompt's end (from the start token without one).
+        constraint= (a markushgrapher_amd.constraint.TokenAutomaton), suppress_tokens=, begin_suppress_tokens=, bad_words_ids=: constrained
+        decoding on the device, greedy and sampled (include/mgrapher.h mg_generate_constrained; rules: _constraint); all given ones are
+        combined, in all three decode modes; output_scores holds the masked scores (greedy, sampled; refused for a constrained beam
+        search).  prefix_allowed_tokens_fn= (pass constraint=), repetition_penalty != 1 and no_repeat_ngram_size > 0 are refused."""
         num_return = int(kw.pop("num_return_sequences", None) or 1)
         as_dict = bool(kw.pop("return_dict_in_generate", False))
         want_scores, want_logits = bool(kw.pop("output_scores", False)), bool(kw.pop("output_logits", False))
@@ -606,9 +676,13 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
         if dec is not None and P is None and (want_scores or want_logits):
             raise ValueError("`output_scores` / `output_logits` with prompts of different lengths are not built: the tuples hold one entry "
                              "per free step of the whole batch")
+        con, con_start = self._constraint(kw, dec, dec_len, int(input_ids.shape[0]))
+        if con is not None and num_beams > 1 and want_scores:
+            raise ValueError("`output_scores` of a constrained beam search is not built (the rows' states follow the beams' reordering on the "
+                             "device); token_scores and sequences_scores hold the masked values")
         if do_sample:
             return self._generate_sampled(input_ids, bbox, pixel_values, attention_mask, num_beams, max_length, min_length, e1, num_return,
-                                          as_dict, want_scores, want_logits, kw, prompt=(dec, dec_len, P))
+                                          as_dict, want_scores, want_logits, kw, prompt=(dec, dec_len, P), con=(con, con_start))
         if num_beams == 1 and num_return > 1:
             raise ValueError(f"Greedy methods without beam search do not support `num_return_sequences` different than 1 (got {num_return}).")
         if num_return > num_beams:
@@ -618,7 +692,8 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
         max_length = int(max_length or self.config.max_length)
         attention_mask = self._default_mask(input_ids, attention_mask)
         gkw = dict(num_beams=num_beams, max_length=max_length, min_length=int(min_length), length_penalty=float(length_penalty),
-                   early_stopping=early_stopping, e1=e1, decoder_prompt=dec, decoder_prompt_len=dec_len)
+                   early_stopping=early_stopping, e1=e1, decoder_prompt=dec, decoder_prompt_len=dec_len, constraint=con,
+                   constraint_start=con_start)
         first = P - 1 if P else 0      # output_scores / output_logits hold the free steps only, as stock's do
         if not as_dict:
             ids, _, _ = eng.generate(input_ids, bbox, attention_mask, pixel_values, num_return=num_return, **gkw)
@@ -649,6 +724,8 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
                 eos = self.config.eos_token_id
                 for t in range(min(steps, max(0, int(min_length) - 1))):
                     sc[t, :, eos] = -float("inf")
+                if con is not None:
+                    self._mask_scores(sc, ids, con, con_start, first, 1)
                 out.scores = tuple(sc[t] for t in range(first, steps))
         return out
 
@@ -683,7 +760,7 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
 
     def generate_queue(self, encodings, max_length=None, min_length=0, slots=32, chunk=32, contexts=1, num_beams=1, length_penalty=1.0,
                        early_stopping=False, num_return_sequences=1, return_scores=False, do_sample=False, temperature=None, top_k=None,
-                       top_p=None, seed=None):
+                       top_p=None, seed=None, **kw):
         """The reference's evaluation loop (ref: utils/ocsr/utils_evaluation.py:140-285) as ONE call: `encodings` = the per-sample
         dicts it builds (input_ids [1, L_n] or [L_n], bbox, pixel_values; attention_mask / labels ignored as there), greedy,
         max_length as there.  Returns a list of 1-D id tensors - predictions[n] == self.generate(**encodings[n], num_beams=1,
@@ -706,6 +783,11 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
         otherwise one dict per image, "sequences" [S, T] (T = the longest sample's columns, shorter ones padded) and "token_scores"
         [S, T - 1] (the log-probability of each drawn token under the warped distribution)."""
         from .assembly import collate_for_generate
+        for k in self._CONSTRAINT_KEYS:      # (constrained decoding belongs to generate(): the queue forms take no constraint)
+            if kw.get(k) is not None:
+                raise ValueError(f"generate_queue: `{k}` is not supported by the queue forms; constrained decoding is built for generate() only")
+        if kw:
+            raise TypeError(f"generate_queue() got an unexpected keyword argument '{next(iter(kw))}'")
         num_beams = int(num_beams)
         nr = int(num_return_sequences or 1)
         if do_sample:
