@@ -238,7 +238,8 @@ int mg_generate_sampled(mg_model* m, void* stream, void* ws, size_t ws_bytes, co
  * mg_sampled_workspace_bytes with rows_per_image = num_return when sampled != 0) plus the [B] lengths, which are validated on the host
  * and uploaded behind the unprompted layout.  ids stay where the caller put them: keep them (and the workspace) in place between calls
  * and a later call of the same shape replays the captured step (pointers and ld are part of its key, the lengths are device data).
- *   NOT built: the queue forms (mg_generate_stream*) and the OCR stage under a prompt; a PREFILL of the prompt - one teacher-forced pass
+ *   The queue forms take a prompt per image: mg_generate_stream_constrained / mg_generate_stream_beam_constrained (below, after the queue forms).
+ *   NOT built: the OCR stage under a prompt; a PREFILL of the prompt - one teacher-forced pass
  * that writes the self-attention cache of all prompt positions would replace len - 1 decode steps, and would give up property (1): its
  * large-M projections sum in another order than the decode step's. */
 typedef struct mg_decoder_prompt {
@@ -278,7 +279,8 @@ int mg_generate_prompted(mg_model* m, void* stream, void* ws, size_t ws_bytes, c
  *   Beam search: the log-softmax stays over the raw logits and the mask sets a candidate's log-probability to -inf where MinLength's EOS is
  * set (stock's order: log_softmax, then the processors); the states of an image's K rows are reordered with the beams.  There is no
  * empty-set rule: -inf candidates are ranked, as in stock, and a beam that takes one moves to the sink.
- *   NOT built: the queue forms (mg_generate_stream*) and the OCR stage
+ *   The queue forms take a constraint with a start state per image: mg_generate_stream_constrained / mg_generate_stream_beam_constrained (below).
+ *   NOT built: the OCR stage
  * under a constraint; the mask inside the fused lm_head epilogue; sparse tables for automata beyond 2^24 entries; forced_eos_token_id;
  * repetition_penalty and no_repeat_ngram_size (they change logit values or need unbounded history: not masks). */
 typedef struct mg_constraint {
@@ -345,6 +347,50 @@ int mg_generate_stream_beam_scored(mg_model* m, void* stream, void* ws, size_t w
                                    const uint8_t* attention_mask, const float* pixel_values, int N, int L, int chunk, int slots, int pool_chunks,
                                    int num_beams, int max_length, int min_length, float length_penalty, int early_stopping, int64_t* out_ids,
                                    int32_t* out_len, long* steps_host, const mg_gen_opts* opts);
+/* The queue forms under a decoder prompt and / or a constraint (mg_decoder_prompt, mg_constraint: see mg_generate_prompted and
+ * mg_generate_constrained).  Greedy and sampled queue: mg_generate_stream_scored's arguments plus samp (nullable; non-NULL selects the sampled queue, whose outputs
+ * are samp's and opts is then ignored), prompt and constraint (both nullable; both NULL is exactly the existing call: same bits, same captured
+ * step).  Prompt and start state are PER IMAGE of the queue - prompt->ids [N][ld] (device), prompt->len_host [N], constraint->start_host [N]
+ * (host) - and shared by the num_return samples of an image.
+ * Beam queue: mg_generate_stream_beam_constrained = mg_generate_stream_beam_scored's arguments plus prompt and constraint (opts nullable).
+ *   Sequence q equals the batch call (mg_generate_constrained, greedy, beam search, or sampled with stream id q) on its image alone with that
+ * image's prompt and start state: ids, length and token_scores bit for bit - for beam search the n-best list, sequence scores and beam_indices
+ * as the queue numbers them - with the cross-attention form pinned, whatever chunk / slots / pool_chunks are.  A prompt of [start] alone and / or an automaton that allows everything give the plain queue's ids, lengths and token scores; a prompt
+ * that is a prefix of what the plain queue writes for its image reproduces it (token scores 0.0 in the forced columns).
+ *   Everything the batch contract says holds per slot row, the owner of a row being the image of the sequence in its slot:
+ *   - a sequence enters its slot with its image's first prompt token where stock puts decoder_start_token_id (column 0 of out_ids holds it)
+ *     and in its image's start state; the slot's previous state is gone with the sequence that left;
+ *   - a forced column takes the prompt's token, never finishes the row (a forced EOS included), draws nothing, scores 0.0 and leaves the
+ *     state alone; min_length counts forced columns; a disallowed token is treated exactly as MinLength's EOS;
+ *   - empty allowed set: the row emits EOS, ends, FREES ITS SLOT, scores 0.0 and is counted; the call completes with every other sequence
+ *     right and returns MG_E_INPUT;
+ *   - a prompt id outside [0, vocab) becomes id 0 and the call returns MG_E_INPUT;
+ *   - "a finished row emits pad and keeps its state" has no counterpart: a finished row leaves.
+ *   Beam search: a newly assigned slot starts as mg_generate_constrained starts its image (the prompt in both sequence arrays, scores
+ * [0, -1e9, ...], the K states at the image's start state, the prompt's first token fed first); the mask follows the log-softmax, the K states
+ * of a slot are reordered with its beams, there is no empty-set rule; the finished-score divisor is (cur_len + 1 - len)^length_penalty and the
+ * early-stop heuristic's length cur_len - len with len the prompt length of the image in the slot; beam_indices hold the image's beam-0
+ * flat row in forced columns, token_scores 0.0.
+ *   A constrained greedy queue runs the selection it always runs (the queue's tail is unfused); the cost is the class loads.
+ *   Checks as the batch functions', MG_E_ARG naming image [n]; the decode-capture instrumentation stays refused (MG_E_STATE) as for all queue
+ * calls.  ids, ld, cls, table, n_states, n_classes and the presence of each are part of the captured step's key; lengths, start states and
+ * states are device data: refilling tables or ids in place and calling again replays the graph, and a plain queue call in between never
+ * replays a constrained step or vice versa.
+ *   WORKSPACE: mg_stream_constrained_workspace_bytes = the queue's size (mg_stream_workspace_bytes; num_beams > 1:
+ * mg_stream_beam_workspace_bytes) plus, behind that layout, the [N] lengths and [N] start states (validated on the host, uploaded by the
+ * call), the [slots * num_beams] states, the class row padded to the logits' row stride and the counters.
+ *   SYNCHRONISES before returning. */
+int mg_stream_constrained_workspace_bytes(const mg_model* m, int chunk, int L, int slots, int pool_chunks, int num_beams, int max_length, int N,
+                                          size_t* out_bytes);
+int mg_generate_stream_constrained(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
+                                   const uint8_t* attention_mask, const float* pixel_values, int N, int L, int chunk, int slots, int pool_chunks,
+                                   int max_length, int min_length, int64_t* out_ids, int32_t* out_len, long* steps_host, const mg_gen_opts* opts,
+                                   const mg_sample_opts* samp, const mg_decoder_prompt* prompt, const mg_constraint* constraint);
+int mg_generate_stream_beam_constrained(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
+                                        const uint8_t* attention_mask, const float* pixel_values, int N, int L, int chunk, int slots,
+                                        int pool_chunks, int num_beams, int max_length, int min_length, float length_penalty, int early_stopping,
+                                        int64_t* out_ids, int32_t* out_len, long* steps_host, const mg_gen_opts* opts,
+                                        const mg_decoder_prompt* prompt, const mg_constraint* constraint);
 /* Where the encoder of mg_generate_stream runs: 0 = on the caller's stream (serial), 1 = own stream at the lowest priority
  * (default), 2 = own stream restricted to the compute units of cu_mask (nwords x 32 bits, hipExtStreamCreateWithCUMask). */
 int mg_stream_encoder_mode(mg_model* m, int mode, const uint32_t* cu_mask, int nwords);
@@ -925,6 +971,34 @@ int mgk_sample_select_constrained(void* stream, const float* logits, int rows, i
                                   int max_len, int pos, const int* pos_dev, int* unfinished, int* n_unfinished, int* step_ctr, float* token_scores,
                                   int ts_ld, float* top2, const mgk_constraint* con, const int64_t* prompt_ids, const int* prompt_len,
                                   int prompt_ld, int group, int* bad);
+/* The greedy / sampled queue forms of the selection step and slot_refill under a decoder prompt and / or a constraint
+ * (mg_generate_stream_constrained).  q NULL, or prompt_ids and con both NULL: the plain operators (mgk_select_ex with a slot table,
+ * mgk_sample_select_queue, mgk_slot_refill), byte for byte.  prompt_ids [images][prompt_ld] / prompt_len [images] / con_start [images] are
+ * per image of the queue, con->state [rows] per slot; the owner of a live row is slots.img[row] / slots.nsamp.  mgk_select_queue_ex needs a
+ * slot table (MG_E_ARG without).  mgk_slot_refill_ex: a slot handed sequence i is fed prompt_ids[i / nsamp][0] (checked against V, counted
+ * in *bad, written to out_ids[i][0] when out_ids [sequences][out_ld] is given) and gets state con_start[i / nsamp]. */
+typedef struct mgk_queue_con {
+    const int64_t* prompt_ids; const int* prompt_len; int prompt_ld, V; int* bad;
+    const mgk_constraint* con;   /* nullable */
+    const int* con_start;
+} mgk_queue_con;
+int mgk_select_queue_ex(void* stream, const mgk_select_desc* s, const mgk_queue_con* q);
+int mgk_sample_select_queue_ex(void* stream, const float* logits, int rows, int V, int ldl, int eos, int pad, int min_len, float temperature,
+                               int top_k, float top_p, uint64_t seed, const uint64_t* stream_ids, int64_t* next_ids, int64_t* out_ids, int max_len,
+                               int* unfinished, float* token_scores, int ts_ld, const mgk_slot_table* slots, const mgk_queue_con* q);
+int mgk_slot_refill_ex(void* stream, const mgk_slot_table* slots, int64_t* next_ids, int* unfinished, int rows, const mgk_queue_con* q,
+                       int64_t* out_ids, int out_ld);
+/* The beam queue under the same: mgk_beam_step in the queue form (slot_pos / slot_live required; slot_img [slots * K] = the image in a
+ * row's slot, required with a prompt) and mgk_beam_slots_step, whose newly assigned slots start as mgk_beam_init_constrained starts the
+ * image they are handed (prompt in both sequence arrays, the K states at con_start[image], the prompt's first token fed first).  cls is
+ * [V] here, con->state [slots * K]; *empty is not used.  q NULL: mgk_beam_step / mgk_beam_slots_step. */
+int mgk_beam_step_queue_ex(void* stream, void* state, const float* logits, int ldl, int V, int B, int K, int max_len, const float* div_table,
+                           int eos, int min_len, float length_penalty, int early_stopping, int64_t* next_ids, int* beam_idx, int* counters,
+                           const int* slot_pos, const int* slot_live, const int* slot_img, const mgk_queue_con* q);
+int mgk_beam_slots_step_ex(void* stream, void* state, int slots, int K, int max_len, int pad, int eos, int start, int early_stopping, int* pos,
+                           int* img, int* pool, int* bpool, int* live, int* assign, int64_t* next_ids, int* anc, int T_cap, int pool_cap,
+                           int64_t* out_ids, int* out_len, float* out_scores, int* ctr, int end_first, int num_return, int* beam_indices,
+                           float* token_scores, const mgk_queue_con* q);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
  * ChemicalOCR stage ("next" row f-1).  Replaces, for the OCR pass that produces the cells the main model

@@ -312,3 +312,64 @@ def one_of(V, eos, sequences):
             table[n, of[int(eos)]] = S - 1
     table[S - 1, of[int(eos)]] = S - 1
     return TokenAutomaton(cls, table, eos)
+
+
+def one_of_each(V, eos, lists):
+    """one automaton for a queue of images with their own candidate lists -> (automaton, starts [N]): a trie per image, all in one table.
+    From state starts[n] exactly the sequences lists[n][j] + [eos] are accepted (candidates as one_of takes them: a trailing EOS is
+    dropped, the start token is not part of a candidate; an empty candidate is the answer [eos]).  Images whose candidate SETS are equal
+    share a root.  Classes: "other", then one per distinct token of all lists and EOS, ascending; the last state is the sink.  One table
+    has to hold every trie: beyond 2**24 entries or 4096 classes a ValueError says how many images (the first k) fit - split the queue
+    there, nothing is split here."""
+    eos = int(eos)
+    sets = []
+    for n, cands in enumerate(lists):
+        seqs = set()
+        for s in cands:
+            s = [int(t) for t in s]
+            if s and s[-1] == eos:
+                s = s[:-1]
+            if eos in s:
+                raise ValueError("a candidate of image %d holds EOS before its end" % n)
+            if s and (min(s) < 0 or max(s) >= V):
+                raise ValueError("token id outside [0, %d)" % V)
+            seqs.add(tuple(s))
+        if not seqs:
+            raise ValueError("image %d has no candidate sequences" % n)
+        sets.append(frozenset(seqs))
+    if not sets:
+        raise ValueError("no images")
+    if eos < 0 or eos >= V:
+        raise ValueError("eos (%d) outside [0, %d)" % (eos, V))
+    children, terminal, root_of, starts = [], [], {}, []
+    tokens = {eos}
+    for n, seqs in enumerate(sets):
+        if seqs not in root_of:
+            root = root_of[seqs] = len(children)
+            children.append({})
+            terminal.append(False)
+            for s in sorted(seqs):
+                m = root
+                for t in s:
+                    if t not in children[m]:
+                        children[m][t] = len(children)
+                        children.append({})
+                        terminal.append(False)
+                    m = children[m][t]
+                terminal[m] = True
+                tokens.update(s)
+            C, S = len(tokens) + 1, len(children) + 1
+            if C > MAX_CLASSES or S * C > MAX_ENTRIES:
+                raise ValueError("the automaton of %d images would have %d states x %d classes (limits: 2**24 entries, %d classes); the first "
+                                 "%d images fit" % (n + 1, S, C, MAX_CLASSES, n))
+        starts.append(root_of[seqs])
+    cls, of = _classes(V, eos, tokens)
+    C, S = len(of) + 1, len(children) + 1
+    table = np.full((S, C), -1, np.int64)
+    for n, ch in enumerate(children):
+        for t, m in ch.items():
+            table[n, of[t]] = m
+        if terminal[n]:
+            table[n, of[eos]] = S - 1
+    table[S - 1, of[eos]] = S - 1
+    return TokenAutomaton(cls, table, eos), np.asarray(starts, np.int32)

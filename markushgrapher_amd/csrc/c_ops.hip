@@ -342,11 +342,14 @@ static int dec_constraint(const mgk_constraint* c, DecConstraint* out) {
     *out = DecConstraint{c->cls, c->table, c->n_states, c->n_classes, c->state, c->empty};
     return MG_OK;
 }
-static int select_impl(void* stream, const mgk_select_desc* s, const DecPrompt& prompt, const DecConstraint& con = DecConstraint{}) {
+static int select_impl(void* stream, const mgk_select_desc* s, const DecPrompt& prompt, const DecConstraint& con = DecConstraint{},
+                       bool queue_ex = false) {
     if (!s || !s->next_ids || !s->out_ids || !s->unfinished) return MG_E_ARG;
     const bool queue = s->slots.pos != nullptr;
-    if (con.cls && (queue || s->fused || s->ptop)) return MG_E_ARG;      // (a constraint belongs to the batch form of the scan: no slot table, no ptop)
-    if (prompt.ids && (queue || !prompt.len || prompt.ld < 1 || prompt.group < 0)) return MG_E_ARG;      // (a prompt belongs to the batch forms)
+    if (queue_ex && !queue) return MG_E_ARG;
+    // (the operators from before the queue forms took a prompt and a constraint keep refusing them with a slot table: mgk_select_queue_ex takes those)
+    if (con.cls && ((queue && !queue_ex) || s->fused || s->ptop)) return MG_E_ARG;      // (a constraint belongs to the scan: no fused tail, no ptop)
+    if (prompt.ids && ((queue && !queue_ex) || !prompt.len || prompt.ld < 1 || prompt.group < 0)) return MG_E_ARG;
     if (s->fused && queue) return MG_E_ARG;                              // (the fused tail has no queue form)
     if (queue ? (!s->slots.img || !s->slots.ctr || !s->slots.out_len) : !s->n_unfinished) return MG_E_ARG;
     if (s->n_eos_more < 0 || s->n_eos_more > 3) return MG_E_ARG;
@@ -448,6 +451,63 @@ int mgk_sample_select_queue(void* stream, const float* logits, int rows, int V, 
     a.next_ids = next_ids; a.out_ids = out_ids; a.max_len = max_len; a.pos = pos; a.unfinished = unfinished;
     a.n_unfinished = n_unfinished; a.token_scores = token_scores; a.ts_ld = ts_ld; a.slots = slot_table(slots);
     sample_select(a, (mgStream_t)stream);
+    return MG_OK;
+}
+// The queue forms under a decoder prompt and / or a constraint (mg_generate_stream_constrained): the prompt and the start states are per
+// image of the queue, the states per slot
+static int queue_con(const mgk_queue_con* q, DecPrompt* dp, DecConstraint* dc) {
+    if (!q) return MG_OK;
+    if (q->prompt_ids) {
+        if (!q->prompt_len || q->prompt_ld < 1 || q->V < 1) return MG_E_ARG;
+        *dp = DecPrompt{q->prompt_ids, q->prompt_len, q->prompt_ld, 1, q->bad};
+    }
+    if (q->con) return dec_constraint(q->con, dc);
+    return MG_OK;
+}
+int mgk_select_queue_ex(void* stream, const mgk_select_desc* s, const mgk_queue_con* q) {
+    DecPrompt dp{};
+    DecConstraint dc{};
+    const int rc = queue_con(q, &dp, &dc);
+    if (rc != MG_OK) return rc;
+    return select_impl(stream, s, dp, dc, true);
+}
+int mgk_sample_select_queue_ex(void* stream, const float* logits, int rows, int V, int ldl, int eos, int pad, int min_len, float temperature,
+                               int top_k, float top_p, uint64_t seed, const uint64_t* stream_ids, int64_t* next_ids, int64_t* out_ids, int max_len,
+                               int* unfinished, float* token_scores, int ts_ld, const mgk_slot_table* slots, const mgk_queue_con* q) {
+    if (!logits || !next_ids || !out_ids || !unfinished || rows < 1 || ldl < V || (ldl & 3)) return MG_E_ARG;
+    if (!(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f)) return MG_E_ARG;
+    if (!slots || !slots->pos || !slots->img || !slots->ctr || !slots->out_len) return MG_E_ARG;
+    if (rows > 256 || max_len < 1 || (token_scores && ts_ld < max_len - 1)) return MG_E_SHAPE;
+    if (!sample_select_supported(V)) return MG_E_UNSUPPORTED;
+    SampleArgs a{};
+    const int rc = queue_con(q, &a.prompt, &a.con);
+    if (rc != MG_OK) return rc;
+    a.logits = logits; a.rows = rows; a.V = V; a.ldl = ldl; a.eos = eos; a.pad = pad; a.min_len = min_len;
+    a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.seed = seed; a.stream_ids = stream_ids;
+    a.next_ids = next_ids; a.out_ids = out_ids; a.max_len = max_len; a.unfinished = unfinished;
+    a.token_scores = token_scores; a.ts_ld = ts_ld; a.slots = slot_table(slots);
+    sample_select(a, (mgStream_t)stream);
+    return MG_OK;
+}
+int mgk_slot_refill_ex(void* stream, const mgk_slot_table* slots, int64_t* next_ids, int* unfinished, int rows, const mgk_queue_con* q,
+                       int64_t* out_ids, int out_ld) {
+    if (!slots || !slots->pos || !slots->img || !slots->pool || !slots->ctr || !slots->out_len || !next_ids || !unfinished) return MG_E_ARG;
+    if (slots->nsamp < 1 || slots->pool_cap < 1 || slots->n_stop < 0 || slots->n_stop > 4) return MG_E_ARG;
+    if (rows < 1 || rows > 256) return MG_E_SHAPE;
+    SlotTable t = slot_table(slots);
+    DecPrompt dp{};
+    DecConstraint dc{};
+    const int rc = queue_con(q, &dp, &dc);
+    if (rc != MG_OK) return rc;
+    if (dp.ids) {
+        if (out_ids && out_ld < 1) return MG_E_ARG;
+        t.q_prompt_ids = dp.ids; t.q_prompt_ld = dp.ld; t.q_V = q->V; t.q_bad = dp.bad; t.q_out_ids = out_ids; t.q_out_ld = out_ld;
+    }
+    if (dc.cls) {
+        if (!q->con_start) return MG_E_ARG;
+        t.q_con_start = q->con_start; t.q_con_state = dc.state;
+    }
+    slot_refill(t, next_ids, unfinished, rows, (mgStream_t)stream);
     return MG_OK;
 }
 int mgk_slot_refill(void* stream, const mgk_slot_table* slots, int64_t* next_ids, int* unfinished, int rows) {
@@ -595,6 +655,40 @@ int mgk_beam_step_constrained(void* stream, void* state, const float* logits, in
     const DecPrompt pr{prompt_ids, prompt_len, prompt_ld, 1, nullptr};
     beam_step(state, logits, ldl, V, B, K, max_len, cur_len, tdev, div_table, eos, min_len, length_penalty, early_stopping, next_ids, beam_idx,
               counters, (mgStream_t)stream, nullptr, prompt_ids ? &pr : nullptr, &dc);
+    return MG_OK;
+}
+// The beam queue under a decoder prompt and / or a constraint (mg_generate_stream_beam_constrained): mgk_beam_step in the queue form and
+// mgk_beam_slots_step with mgk_queue_con - prompt and start state per image of the queue (slot_img [slots * K] names the image in a row's
+// slot), con->state [slots * K] per slot row.  q NULL or empty: the plain operators.
+int mgk_beam_step_queue_ex(void* stream, void* state, const float* logits, int ldl, int V, int B, int K, int max_len, const float* div_table,
+                           int eos, int min_len, float length_penalty, int early_stopping, int64_t* next_ids, int* beam_idx, int* counters,
+                           const int* slot_pos, const int* slot_live, const int* slot_img, const mgk_queue_con* q) {
+    if (!beam_geometry_ok(B, K, max_len) || V < 2 * K || ldl < V) return MG_E_SHAPE;
+    if (!slot_pos || !slot_live || !div_table) return MG_E_ARG;
+    DecPrompt dp{};
+    DecConstraint dc{};
+    const int rc = queue_con(q, &dp, &dc);
+    if (rc != MG_OK) return rc;
+    if (dp.ids && !slot_img) return MG_E_ARG;
+    const BeamSlots bs{slot_pos, slot_live, slot_img};
+    beam_step(state, logits, ldl, V, B, K, max_len, 0, nullptr, div_table, eos, min_len, length_penalty, early_stopping, next_ids, beam_idx,
+              counters, (mgStream_t)stream, &bs, dp.ids ? &dp : nullptr, dc.cls ? &dc : nullptr);
+    return MG_OK;
+}
+int mgk_beam_slots_step_ex(void* stream, void* state, int slots, int K, int max_len, int pad, int eos, int start, int early_stopping, int* pos,
+                           int* img, int* pool, int* bpool, int* live, int* assign, int64_t* next_ids, int* anc, int T_cap, int pool_cap,
+                           int64_t* out_ids, int* out_len, float* out_scores, int* ctr, int end_first, int num_return, int* beam_indices,
+                           float* token_scores, const mgk_queue_con* q) {
+    if (!beam_geometry_ok(slots, K, max_len) || T_cap < max_len - 1 || pool_cap < 1 || num_return < 1 || num_return > K) return MG_E_SHAPE;
+    DecPrompt dp{};
+    DecConstraint dc{};
+    const int rc = queue_con(q, &dp, &dc);
+    if (rc != MG_OK) return rc;
+    if (dc.cls && !q->con_start) return MG_E_ARG;
+    const BeamOut nb{num_return, beam_indices, token_scores};
+    beam_slots_step(state, slots, K, max_len, pad, eos, start, early_stopping, pos, img, pool, bpool, live, assign, next_ids, anc, T_cap, pool_cap,
+                    out_ids, out_len, out_scores, ctr, end_first != 0, (mgStream_t)stream, &nb, dp.ids ? &dp : nullptr, q ? q->V : 0,
+                    dc.cls ? dc.state : nullptr, dc.cls ? q->con_start : nullptr);
     return MG_OK;
 }
 int mgk_beam_reorder_anc(void* stream, int* anc, const int* beam_idx, int rows, int t_written, const int* tdev, const int* counters,

@@ -89,9 +89,14 @@ struct QueueStepKey {        // mg_generate_stream*: greedy, sampled and beam qu
     float temperature, top_p;
     uint64_t seed;
     const void* stream_ids;
+    // prompted / constrained queue (mg_generate_stream_constrained): the selection and the refill launches hold the caller's pointers and
+    // sizes (lengths, start states and states are device data in the workspace); absent: all 0, so a plain call never replays such a step
+    const void *prompt_ids, *con_cls, *con_table;
+    int prompt_ld, con_states, con_classes;
+    bool has_prompt, has_con;
     MG_KEY_MEMBERS(QueueStepKey, ws, out_ids, out_len, stream, N, L, chunk, slots, pool_chunks, num_beams, max_length, min_length,
                    early_stopping, length_penalty, out_scores, token_scores, beam_indices, num_return, top_k, temperature, top_p, seed,
-                   stream_ids)
+                   stream_ids, prompt_ids, con_cls, con_table, prompt_ld, con_states, con_classes, has_prompt, has_con)
 };
 
 struct mg_model {
@@ -833,13 +838,13 @@ static void decode_step(mg_model* m, const DecodeCtx& c, int t, const int* tdev,
             MG_LAUNCH(force_ids_kernel, dim3((R + 63) / 64), dim3(64), 0, st, c.next_ids, m->dbg_forced, R, max_length, t + 1);
     } else if (stream) {
         // queue form: every slot at its own length; stopped images are written out and their slots handed to the next images
-        const BeamSlots bs{c.slots.pos, c.unfinished};
+        const BeamSlots bs{c.slots.pos, c.unfinished, c.slots.img};
         beam_step(c.beam_state, c.logits, ldl, m->V, B, K, max_length, 0, nullptr, c.beam_div, m->c.eos_token_id, min_length,
-                  length_penalty, early_stopping, c.next_ids, c.beam_idx, counters, st, &bs);
+                  length_penalty, early_stopping, c.next_ids, c.beam_idx, counters, st, &bs, &c.prompt, &c.con);
         beam_reorder_anc(c.anc, c.beam_idx, R, max_length - 1, nullptr, counters, st, &bs);
         beam_slots_step(c.beam_state, B, K, max_length, (int)pad, m->c.eos_token_id, c.slots.start_id, early_stopping, c.slots.pos, c.slots.img,
                         c.slots.pool, c.bpool, c.unfinished, c.assign, c.next_ids, c.anc, T_cap, c.slots.pool_cap, out_ids, c.out_len,
-                        c.out_scores, c.slots.ctr, true, st, &c.nbest);
+                        c.out_scores, c.slots.ctr, true, st, &c.nbest, c.prompt.ids ? &c.prompt : nullptr, m->V, c.con.state, c.slots.q_con_start);
     } else {
         beam_step(c.beam_state, c.logits, ldl, m->V, B, K, max_length, t + 1, tdev, c.beam_div, m->c.eos_token_id, min_length,
                   length_penalty, early_stopping, c.next_ids, c.beam_idx, counters, st, nullptr, &c.prompt, &c.con);
@@ -1443,6 +1448,9 @@ static size_t prompt_ws_bytes(int B) { return align_up((size_t)B * sizeof(int32_
 static size_t con_state_bytes(int rows) { return align_up((size_t)rows * sizeof(int32_t), 256); }
 static size_t con_cls_bytes(int V) { return align_up((size_t)round_up(V, 32) * sizeof(uint16_t), 256); }
 static size_t con_ws_bytes(int rows, int V) { return con_state_bytes(rows) + con_cls_bytes(V) + 256; }
+// mg_generate_stream_constrained, behind the plain queue's layout: the images' prompt lengths [N] and start states [N], then as above with
+// one state per decode row of the slot table
+static size_t stream_con_ws_bytes(int N, int rows, int V) { return 2 * prompt_ws_bytes(N) + con_ws_bytes(rows, V); }
 
 // owner[r] = r / group: the image whose encoder states row r of a sampled call reads
 __global__ void row_owner_kernel(int* owner, int rows, int group) {
@@ -1782,7 +1790,8 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
                                 const uint8_t* attention_mask, const float* pixel_values, int N, int L, int chunk, int slots, int pool_chunks,
                                 int K, int max_length, int min_length, float length_penalty, int early_stopping, int64_t* out_ids,
                                 int32_t* out_len, float* out_scores, long* steps_host, const char* who, const mg_gen_opts* opts,
-                                const mg_sample_opts* samp = nullptr) {
+                                const mg_sample_opts* samp = nullptr, const mg_decoder_prompt* prompt = nullptr,
+                                const mg_constraint* con = nullptr) {
     entry_drain();
     if (!m || !ws || !input_ids || !bbox || !pixel_values || !out_ids || !out_len) return fail(MG_E_ARG, "%s: null argument", who);
     MG_ONE_CALL(m, "mg_generate_stream");
@@ -1810,9 +1819,32 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
     float* token_scores = samp ? samp->token_scores : (opts ? opts->token_scores : nullptr);
     if (opts && K > 1) out_scores = opts->seq_scores;
     const int R = slots * K;                         // decode rows
+    // prompt and constraint: the batch functions' checks, per image of the queue
+    if (prompt) {
+        if (!prompt->ids || !prompt->len_host || prompt->ld < 1) return fail(MG_E_ARG, "%s: decoder prompt needs ids, len_host and ld >= 1", who);
+        for (int n = 0; n < N; ++n) {
+            const int len = prompt->len_host[n];
+            if (len < 1 || len > prompt->ld)
+                return fail(MG_E_ARG, "%s: decoder prompt length of image %d (%d) must be in [1, ld = %d]", who, n, len, prompt->ld);
+            if (len >= max_length)
+                return fail(MG_E_ARG, "%s: decoder prompt length of image %d (%d) must be below max_length (%d)", who, n, len, max_length);
+        }
+    }
+    if (con) {
+        if (!con->cls || !con->table || !con->start_host) return fail(MG_E_ARG, "%s: constraint needs cls, table and start_host", who);
+        if (con->n_classes < 1 || con->n_classes > DEC_CON_MAX_CLASSES)
+            return fail(MG_E_ARG, "%s: constraint n_classes (%d) must be in [1, %d]", who, con->n_classes, DEC_CON_MAX_CLASSES);
+        if (con->n_states < 2) return fail(MG_E_ARG, "%s: constraint n_states (%d) must be >= 2 (the last state is the sink)", who, con->n_states);
+        if ((long long)con->n_states * con->n_classes > (1ll << 24))
+            return fail(MG_E_ARG, "%s: constraint table of %d x %d entries exceeds 2^24", who, con->n_states, con->n_classes);
+        for (int n = 0; n < N; ++n)
+            if (con->start_host[n] < 0 || con->start_host[n] >= con->n_states)
+                return fail(MG_E_ARG, "%s: start state of image %d (%d) must be in [0, n_states = %d)", who, n, con->start_host[n], con->n_states);
+    }
     StreamWs w;
     carve_stream(m, (char*)ws, chunk, L, slots, pool_chunks, &w, K, max_length);
-    if (w.total > ws_bytes) return fail(MG_E_WORKSPACE, "%s: workspace too small (%zu < %zu)", who, ws_bytes, w.total);
+    const size_t ws_need = w.total + ((prompt || con) ? stream_con_ws_bytes(N, R, m->V) : 0);
+    if (ws_need > ws_bytes) return fail(MG_E_WORKSPACE, "%s: workspace too small (%zu < %zu)", who, ws_bytes, ws_need);
     mgStream_t st = (mgStream_t)stream;
     const int H = m->H, P = m->P;
     const int S_cap = round_up(L + P, 64), M64 = round_up(m->e1_M, 64), Sx_cap = S_cap + M64;
@@ -1863,6 +1895,35 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
     dc.nbest = BeamOut{num_return, opts ? opts->beam_indices : nullptr, K > 1 ? token_scores : nullptr};
     dc.slots = SlotTable{w.pos, w.img, w.pool, w.ctr, out_len, entries, (int)start};
     dc.slots.nsamp = S;
+    // Prompt and constraint: the extras lie behind the plain queue's layout - lengths [N] | start states [N] | slot states [R] | class row |
+    // counters {empty sets, bad prompt ids}.  The validated host arrays go up from vectors of the context's (the call ends with a host
+    // synchronisation of st); every slot state is a valid index from here on (0), whether its slot is ever live or not.
+    int* qc_ctr = nullptr;
+    if (prompt || con) {
+        char* base = (char*)ws + w.total;
+        int* len_dev = (int*)base;
+        int* start_dev = (int*)(base + prompt_ws_bytes(N));
+        int* state_dev = (int*)(base + 2 * prompt_ws_bytes(N));
+        uint16_t* cls_dev = (uint16_t*)(base + 2 * prompt_ws_bytes(N) + con_state_bytes(R));
+        qc_ctr = (int*)(base + 2 * prompt_ws_bytes(N) + con_state_bytes(R) + con_cls_bytes(m->V));
+        mg_memset_async(qc_ctr, 0, 2 * sizeof(int), st);
+        if (prompt) {
+            m->prompt_len_host.assign(prompt->len_host, prompt->len_host + N);
+            mg_memcpy_async(len_dev, m->prompt_len_host.data(), (size_t)N * sizeof(int32_t), st);
+            dc.prompt = DecPrompt{prompt->ids, len_dev, prompt->ld, 1, qc_ctr + 1};
+            dc.slots.q_prompt_ids = prompt->ids; dc.slots.q_prompt_ld = prompt->ld; dc.slots.q_V = m->V; dc.slots.q_bad = qc_ctr + 1;
+            dc.slots.q_out_ids = out_ids; dc.slots.q_out_ld = max_length;
+        }
+        if (con) {
+            m->con_start_host.assign(con->start_host, con->start_host + N);
+            mg_memcpy_async(start_dev, m->con_start_host.data(), (size_t)N * sizeof(int32_t), st);
+            mg_memset_async(state_dev, 0, con_state_bytes(R), st);
+            mg_memset_async(cls_dev, 0, con_cls_bytes(m->V), st);
+            mg_memcpy_async(cls_dev, con->cls, (size_t)m->V * sizeof(uint16_t), st);
+            dc.con = DecConstraint{cls_dev, con->table, con->n_states, con->n_classes, state_dev, qc_ctr};
+            dc.slots.q_con_start = start_dev; dc.slots.q_con_state = state_dev;
+        }
+    }
     // the step as a graph (every step-dependent value lives in the slot table)
     bool graphed = false;
     if (m->use_graph == 1) {
@@ -1875,6 +1936,8 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
             key.num_return = S; key.top_k = samp->top_k; key.temperature = samp->temperature; key.top_p = samp->top_p; key.seed = samp->seed;
             key.stream_ids = samp->stream_ids;
         }
+        if (prompt) { key.has_prompt = true; key.prompt_ids = prompt->ids; key.prompt_ld = prompt->ld; }
+        if (con) { key.has_con = true; key.con_cls = con->cls; key.con_table = con->table; key.con_states = con->n_states; key.con_classes = con->n_classes; }
         graphed = m->stream_graph.ensure(key, st, who, [&] { decode_step(m, dc, 0, nullptr, false, st); });
     }
     m->graph_active = graphed;
@@ -1951,7 +2014,9 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
     }
     int err2[2] = {0, 0};
     int& err_host = err2[0];
+    int qc_host[2] = {0, 0};                 // {rows that met an empty allowed set, prompt ids outside the vocabulary}
     if (es != st) mg_stream_sync(es);
+    if (qc_ctr) mg_memcpy_async(qc_host, qc_ctr, 2 * sizeof(int), st);
     mg_memcpy_async(err2, w.err, 2 * sizeof(int), st);
     mg_stream_sync(st);
     rc = check_launch(who);
@@ -1962,11 +2027,33 @@ static int generate_stream_impl(mg_model* m, void* stream, void* ws, size_t ws_b
     if (m->prof_used) accumulate_cross_profile(m, (double)err2[1] / N * (NQ < slots ? NQ : slots));
     m->stream_steps = steps;
     if (steps_host) *steps_host = steps;
-    if (err_host != 0) return fail(MG_E_INPUT, "%s: %d token ids outside [0, vocab)", who, err_host);
+    if (err_host + qc_host[1] != 0) return fail(MG_E_INPUT, "%s: %d token ids outside [0, vocab)", who, err_host + qc_host[1]);      // (encoder ids and prompt ids)
+    if (qc_host[0] != 0)      // (the outputs are complete: such a sequence holds EOS where its allowed set was empty)
+        return fail(MG_E_INPUT, "%s: %d sequences reached a state that allows no token (an EOS-only state below min_length; or no allowed token had a finite logit)", who, qc_host[0]);
     return MG_OK;
 }
 
 extern "C" {
+
+int mg_stream_constrained_workspace_bytes(const mg_model* m, int chunk, int L, int slots, int pool_chunks, int num_beams, int max_length, int N,
+                                          size_t* out_bytes) {
+    if (!m || !out_bytes || N < 1) return fail(MG_E_ARG, "mg_stream_constrained_workspace_bytes: null argument or N < 1");
+    size_t base = 0;
+    const int rc = num_beams > 1 ? mg_stream_beam_workspace_bytes(m, chunk, L, slots, pool_chunks, num_beams, max_length, &base)
+                                 : mg_stream_workspace_bytes(m, chunk, L, slots, pool_chunks, &base);
+    if (rc != MG_OK) return rc;
+    *out_bytes = base + stream_con_ws_bytes(N, slots * (num_beams > 1 ? num_beams : 1), m->V);
+    return MG_OK;
+}
+int mg_generate_stream_constrained(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
+                                   const uint8_t* attention_mask, const float* pixel_values, int N, int L, int chunk, int slots, int pool_chunks,
+                                   int max_length, int min_length, int64_t* out_ids, int32_t* out_len, long* steps_host, const mg_gen_opts* opts,
+                                   const mg_sample_opts* samp, const mg_decoder_prompt* prompt, const mg_constraint* constraint) {
+    const char* who = (prompt || constraint) ? "mg_generate_stream_constrained" : (samp ? "mg_generate_stream_sampled" : "mg_generate_stream");
+    return generate_stream_impl(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, N, L, chunk, slots, pool_chunks, 1,
+                                max_length, min_length, 1.0f, 0, out_ids, out_len, nullptr, steps_host, who, samp ? nullptr : opts, samp, prompt,
+                                constraint);
+}
 
 int mg_generate_stream(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
                        const uint8_t* attention_mask, const float* pixel_values, int N, int L, int chunk, int slots, int pool_chunks,
@@ -2015,6 +2102,16 @@ int mg_generate_stream_beam_scored(mg_model* m, void* stream, void* ws, size_t w
     return generate_stream_impl(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, N, L, chunk, slots, pool_chunks,
                                 num_beams, max_length, min_length, length_penalty, early_stopping, out_ids, out_len, nullptr, steps_host,
                                 "mg_generate_stream_beam", opts);
+}
+int mg_generate_stream_beam_constrained(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* input_ids, const float* bbox,
+                                        const uint8_t* attention_mask, const float* pixel_values, int N, int L, int chunk, int slots,
+                                        int pool_chunks, int num_beams, int max_length, int min_length, float length_penalty, int early_stopping,
+                                        int64_t* out_ids, int32_t* out_len, long* steps_host, const mg_gen_opts* opts,
+                                        const mg_decoder_prompt* prompt, const mg_constraint* constraint) {
+    return generate_stream_impl(m, stream, ws, ws_bytes, input_ids, bbox, attention_mask, pixel_values, N, L, chunk, slots, pool_chunks,
+                                num_beams, max_length, min_length, length_penalty, early_stopping, out_ids, out_len, nullptr, steps_host,
+                                (prompt || constraint) ? "mg_generate_stream_beam_constrained" : "mg_generate_stream_beam", opts, nullptr, prompt,
+                                constraint);
 }
 
 // Live timing of the dominant decode kernel (single-query cross-attention over the image K/V stream): when enabled,

@@ -167,7 +167,8 @@ __global__ __launch_bounds__(BT_THREADS) void beam_row_topk_kernel(BeamPtrs p, c
     // continue flag
     if (bs.pos ? bs.live[blockIdx.x] == 0 : counters[0] == 0) return;
     const int cur_len = bs.pos ? bs.pos[blockIdx.x] + 1 : (tdev ? *tdev + 1 : cur_len_arg);
-    if (pr.ids && cur_len < pr.len[blockIdx.x / K]) return;      // a forced column of the image's prompt: nothing is ranked
+    // (queue form: the owner of a live slot's rows is the image in the slot; resolved behind the live test - an idle slot holds image -1)
+    if (pr.ids && cur_len < pr.len[bs.pos ? bs.img[blockIdx.x] : blockIdx.x / K]) return;      // a forced column of the image's prompt: nothing is ranked
     MG_DYN_SMEM(smem);
     float* red = (float*)smem;            // [16]
     float* selv = red + 16;               // [16]
@@ -268,7 +269,7 @@ __global__ __launch_bounds__(BT_THREADS) void beam_row_topk_kernel(BeamPtrs p, c
 __global__ __launch_bounds__(128) void beam_merge_topk_kernel(BeamPtrs p, int K, const int* counters, BeamSlots bs, int cur_len_arg,
                                                          const int* tdev, DecPrompt pr) {
     if (bs.pos ? bs.live[blockIdx.x * K] == 0 : counters[0] == 0) return;
-    if (pr.ids && (tdev ? *tdev + 1 : cur_len_arg) < pr.len[blockIdx.x]) return;
+    if (pr.ids && (bs.pos ? bs.pos[blockIdx.x * K] + 1 < pr.len[bs.img[blockIdx.x * K]] : (tdev ? *tdev + 1 : cur_len_arg) < pr.len[blockIdx.x])) return;
     MG_DYN_SMEM(smem);
     const int b = blockIdx.x, tid = threadIdx.x, keep = 2 * K, n = K * keep;
     float* cv = (float*)smem;             // [128]
@@ -292,7 +293,7 @@ __global__ __launch_bounds__(256) void beam_update_kernel(BeamPtrs p, int B, int
     // Decoder prompt: stock's decoder_prompt_len of THIS image (1 without a prompt).  A forced column appends the prompt's token (in the
     // sequence arrays since beam_init) to every beam: the beam index is the identity, running scores and the finished set stay as they
     // are, and the image's loop condition says "continue" (it has not ranked anything yet).
-    const int plen = pr.ids ? pr.len[blockIdx.x] : 1;
+    const int plen = pr.ids ? pr.len[bs.pos ? bs.img[blockIdx.x * K] : blockIdx.x] : 1;      // (queue form: the length of the image in the slot)
     if (cur_len < plen) {
         const int b = blockIdx.x, tid = threadIdx.x;
         if (tid < K) {
@@ -480,9 +481,10 @@ void beam_step(void* state, const float* logits, int ldl, int V, int B, int K, i
                int* beam_idx, int* counters, mgStream_t stream, const BeamSlots* slots, const DecPrompt* prompt, const DecConstraint* con) {
     const BeamPtrs p = beam_ptrs(state, B, K, max_len);
     const BeamSlots bs = slots ? *slots : BeamSlots{nullptr, nullptr};
-    // a prompt belongs to the batch form and always takes its divisor from div_table (the prompt lengths live on the device)
-    const DecPrompt pr = (prompt && !bs.pos) ? *prompt : DecPrompt{};
-    const DecConstraint dc = (con && con->cls && !bs.pos) ? *con : DecConstraint{};      // (a constraint belongs to the batch form)
+    // a prompt always takes its divisor from div_table (the prompt lengths live on the device).  Queue form: one prompt / start state per
+    // image of the queue (BeamSlots::img names the image in a slot), one state per slot row
+    const DecPrompt pr = (prompt && (!bs.pos || bs.img)) ? *prompt : DecPrompt{};
+    const DecConstraint dc = (con && con->cls) ? *con : DecConstraint{};
     if (dc.cls)
         MG_LAUNCH((beam_row_topk_kernel<true>), dim3(B * K), dim3(BT_THREADS), 256 + (size_t)dc.n_classes * sizeof(int), stream, p, logits, ldl, V, K,
                   cur_len, eos, min_len, (const int*)counters, tdev, bs, pr, dc);
@@ -610,18 +612,29 @@ __global__ __launch_bounds__(64) void beam_slot_assign_kernel(int slots, int K, 
 }
 __global__ __launch_bounds__(256) void beam_slot_init_kernel(BeamPtrs p, int slots, int K, int max_len, int fill, int start, const int* assign,
                                                         int* pos, int* img, int* pool, int* bpool, int* live, int64_t* next_ids, int* anc,
-                                                        int T_cap, int pool_cap) {
+                                                        int T_cap, int pool_cap, DecPrompt pr, int V, int* con_state, const int* con_start) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const int a = assign[b];
     if (a < 0) return;
     const int R = slots * K;
+    // prompt / constraint: beam_init_kernel's values for image a in slot b - its prompt in both sequence arrays, the slot's beam-0 row and
+    // log-probability 0 in the forced columns' histories, its start state in the K rows, its first prompt token fed first
+    const int plen = pr.ids ? pr.len[a] : 0;
     for (int i = tid; i < K * max_len; i += 256) {
-        const int64_t v = (i % max_len == 0) ? start : fill;
+        const int j = i % max_len;
+        int64_t v = (j == 0) ? start : fill;
+        if (j < plen) {
+            v = pr.ids[(size_t)a * pr.ld + j];
+            if (v < 0 || v >= (int64_t)V) {
+                if (i < max_len && pr.bad) atomicAdd(pr.bad, 1);      // once per (image, column)
+                v = 0;
+            }
+        }
         p.running_seq[(size_t)b * K * max_len + i] = v;
         p.sequences[(size_t)b * K * max_len + i] = v;
     }
     for (int i = tid; i < K * (max_len - 1); i += 256) {
-        p.run_idx[(size_t)b * K * (max_len - 1) + i] = -1;
+        p.run_idx[(size_t)b * K * (max_len - 1) + i] = (i % (max_len - 1)) < plen - 1 ? b * K : -1;
         p.beam_idx_out[(size_t)b * K * (max_len - 1) + i] = -1;
         p.run_lp[(size_t)b * K * (max_len - 1) + i] = 0.f;
         p.lp_out[(size_t)b * K * (max_len - 1) + i] = 0.f;
@@ -630,7 +643,13 @@ __global__ __launch_bounds__(256) void beam_slot_init_kernel(BeamPtrs p, int slo
         p.running_scores[b * K + i] = i == 0 ? 0.f : -1.0e9f;
         p.beam_scores[b * K + i] = -1.0e9f;
         p.is_fin[b * K + i] = 0;
-        next_ids[b * K + i] = start;
+        int64_t first = start;
+        if (plen > 0) {
+            first = pr.ids[(size_t)a * pr.ld];
+            if (first < 0 || first >= (int64_t)V) first = 0;
+        }
+        next_ids[b * K + i] = first;
+        if (con_state) con_state[b * K + i] = con_start[a];      // (the state of the image that left the slot is gone with it)
         pos[b * K + i] = 0; img[b * K + i] = a; pool[b * K + i] = a % pool_cap; live[b * K + i] = 1;
     }
     for (int i = tid; i < T_cap * K; i += 256) {   // identity ancestor table for this slot's rows
@@ -645,7 +664,8 @@ __global__ __launch_bounds__(256) void beam_slot_init_kernel(BeamPtrs p, int slo
 }
 void beam_slots_step(void* state, int slots, int K, int max_len, int pad, int eos, int start, int early_stopping, int* pos, int* img, int* pool,
                      int* bpool, int* live, int* assign, int64_t* next_ids, int* anc, int T_cap, int pool_cap, int64_t* out_ids, int* out_len,
-                     float* out_scores, int* ctr, bool end_first, mgStream_t stream, const BeamOut* nbest) {
+                     float* out_scores, int* ctr, bool end_first, mgStream_t stream, const BeamOut* nbest, const DecPrompt* prompt, int V,
+                     int* con_state, const int* con_start) {
     const BeamPtrs p = beam_ptrs(state, slots, K, max_len);
     BeamOut nb = nbest ? *nbest : BeamOut{1, nullptr, nullptr};
     if (nb.num_return < 1 || nb.num_return > K) nb.num_return = 1;
@@ -654,7 +674,7 @@ void beam_slots_step(void* state, int slots, int K, int max_len, int pad, int eo
                   ctr, nb);
     MG_LAUNCH(beam_slot_assign_kernel, dim3(1), dim3(64), 0, stream, slots, K, (const int*)live, (const int*)img, assign, ctr);
     MG_LAUNCH(beam_slot_init_kernel, dim3(slots), dim3(256), 0, stream, p, slots, K, max_len, pad ? pad : eos, start, (const int*)assign, pos, img,
-              pool, bpool, live, next_ids, anc, T_cap, pool_cap);
+              pool, bpool, live, next_ids, anc, T_cap, pool_cap, prompt ? *prompt : DecPrompt{}, V, con_start ? con_state : (int*)nullptr, con_start);
 }
 
 // physical reorder (cache_utils.py:100-104): dst[lk][r] = src[lk][beam_idx[r]], 16-byte copies, HBM-bound

@@ -374,7 +374,7 @@ MG_DEV void lse_merge(float& m, float& s, float m2, float s2) {
     else if (m2 > m) { s = s * expf(m - m2) + s2; m = m2; }
     else s += s2 * expf(m2 - m);
 }
-// CON (batch form, DecConstraint in mg_kernels.h): the table row of the row's state is staged in LDS once per launch (at most 16 KB); a
+// CON (DecConstraint in mg_kernels.h; queue form: state[row] is staged for idle slots too, so it is a valid state at all times): the table row of the row's state is staged in LDS once per launch (at most 16 KB); a
 // token lane loads the classes of its four tokens beside their logits, and a token whose entry is -1 is treated exactly as a suppressed
 // EOS: it cannot win and is left out of top2 and of the token-score normaliser.  CON = false is the kernel as it was.
 template <bool CON>
@@ -468,14 +468,28 @@ __global__ __launch_bounds__(GS_THREADS) void greedy_select_kernel(ArgmaxArgs a)
         if (stream) {
             // continuous decoding: the row writes column `pos` of ITS image; a row that ends frees the slot (slot_refill hands
             // it the next image).  Idle slots computed on stale inputs: nothing is written for them.
+            // Prompt and constraint as in the batch branch below, store for store; the owner of the row is the image of the sequence in
+            // its slot (resolved here, for a live row only: an idle slot holds image -1).  A row that ends leaves: no state is kept for it.
             if (a.unfinished[row]) {
                 const int img = a.slots.img[row];
-                const int64_t tok = (int64_t)i1;
+                int64_t tok = (int64_t)i1;
+                const bool forced = prompt_forced_owner(a.prompt, a.slots.nsamp > 1 ? img / a.slots.nsamp : img, pos, a.V, tok);
+                bool scored = !forced;
+                if (CON && scored) {
+                    if (b1 == -3.0e38f) {       // empty allowed set: EOS ends the row (and frees the slot), score 0.0
+                        tok = (int64_t)a.eos;
+                        scored = false;
+                        a.con.state[row] = a.con.n_states - 1;
+                        atomicAdd(a.con.empty, 1);
+                    } else {
+                        a.con.state[row] = trow[a.con.cls[tok]];
+                    }
+                }
                 a.next_ids[row] = tok;
                 a.slots.pos[row] = pos;
                 if (pos < a.max_len) a.out_ids[(size_t)img * a.max_len + pos] = tok;
-                if (a.token_scores && pos < a.max_len) a.token_scores[(size_t)img * a.ts_ld + pos - 1] = -logf(se);
-                if (is_eos((int)tok) || pos + 1 >= a.max_len) {
+                if (a.token_scores && pos < a.max_len) a.token_scores[(size_t)img * a.ts_ld + pos - 1] = scored ? -logf(se) : 0.f;
+                if ((!forced && is_eos((int)tok)) || pos + 1 >= a.max_len) {
                     a.unfinished[row] = 0;
                     a.slots.img[row] = -1;
                     a.slots.out_len[img] = pos + 1 < a.max_len ? pos + 1 : a.max_len;
@@ -552,6 +566,18 @@ __global__ __launch_bounds__(64) void slot_refill_kernel(SlotTable s, int64_t* n
                 for (int k = 0; k < s.n_stop; ++k) stop = stop || t == s.stop[k];
                 if (stop) { s.out_len[i] = 1; ++done_add; continue; }
             }
+            const int owner = S > 1 ? i / S : i;
+            if (s.q_prompt_ids) {
+                // decoder prompt: the sequence starts with its image's first prompt token where stock puts decoder_start_token_id
+                // (column 0 is forced whatever the prompt's length: 1 <= len), checked as prompt_forced checks the later columns
+                tok = s.q_prompt_ids[(size_t)owner * s.q_prompt_ld];
+                if (tok < 0 || tok >= (int64_t)s.q_V) {
+                    if (s.q_bad) atomicAdd(s.q_bad, 1);
+                    tok = 0;
+                }
+                if (s.q_out_ids) s.q_out_ids[(size_t)i * s.q_out_ld] = tok;
+            }
+            if (s.q_con_state) s.q_con_state[r] = s.q_con_start[owner];      // constraint: the new sequence starts in its image's start state
             s.img[r] = i;
             s.pool[r] = (i / S) % s.pool_cap;
             s.pos[r] = 0;
@@ -699,7 +725,7 @@ void greedy_select_fused(const ArgmaxArgs& a, mgStream_t stream) {
 }
 
 void greedy_select(const ArgmaxArgs& a, mgStream_t stream) {
-    if (a.con.cls)      // (batch form; the callers refuse a slot table and more than DEC_CON_MAX_CLASSES classes)
+    if (a.con.cls)      // (batch and queue forms; the callers refuse more than DEC_CON_MAX_CLASSES classes)
         MG_LAUNCH((greedy_select_kernel<true>), dim3(a.rows), dim3(GS_THREADS), 512 + (size_t)a.con.n_classes * sizeof(int), stream, a);
     else
         MG_LAUNCH((greedy_select_kernel<false>), dim3(a.rows), dim3(GS_THREADS), 512, stream, a);

@@ -111,7 +111,9 @@ MG_DEV uint32_t ss_radix_select(const uint32_t (&keys)[NQ * 4], const uint32_t (
 
 // QUEUE: the continuous decoder's form (SampleArgs::slots, mg_kernels.h) - the row's column, output row and random stream are those of
 // the sequence in the slot (three wave-uniform scalars); everything that decides the token is the batch form's code.
-// CON (batch form, DecConstraint in mg_kernels.h): the tokens the row's state does not allow become -inf where MinLength's EOS does, in
+// QUEUE under a prompt / constraint: the owner of a live row is the image of its sequence, seq / slots.nsamp; a forced column and the
+// empty-set rule are the batch form's, and a row that ends frees its slot as ever.
+// CON (DecConstraint in mg_kernels.h): the tokens the row's state does not allow become -inf where MinLength's EOS does, in
 // the registers that hold the row, before temperature, top-k, top-p and the draw; the draw's counter and stream are unchanged.
 template <int NQ, int NT, bool QUEUE, bool CON = false>
 __global__ __launch_bounds__(NT) void sample_select_kernel(SampleArgs a) {
@@ -135,13 +137,14 @@ __global__ __launch_bounds__(NT) void sample_select_kernel(SampleArgs a) {
     // decoder prompt (batch form): a row in a forced column neither scans nor draws - thread 0 writes the prompt's token with score 0 and
     // the row stays live; it takes part in the step's counters exactly as a free row does
     bool forced = false;
-    if (!QUEUE && a.prompt.ids) forced = pos < a.prompt.len[a.prompt.group > 1 ? row / a.prompt.group : row];
+    const int owner = QUEUE ? (a.slots.nsamp > 1 ? seq / a.slots.nsamp : seq) : (a.prompt.group > 1 ? row / a.prompt.group : row);
+    if (a.prompt.ids && (!QUEUE || unf)) forced = pos < a.prompt.len[owner];      // (queue form: an idle slot has no owner)
     if (forced) {
         // Every thread has read the step counter (pos) before thread 0 may advance it: the last workgroup to arrive increments *pos_dev in
         // its bookkeeping below, and a thread of this workgroup that read it afterwards would no longer see a forced column.  (A free row
         // has its scan's barriers between the two; a finished row never looks at pos again.)
         __syncthreads();
-        if (tid == 0) prompt_forced(a.prompt, row, pos, a.V, tok);
+        if (tid == 0) prompt_forced_owner(a.prompt, owner, pos, a.V, tok);
     } else if (unf) {
         const float* lg = a.logits + (size_t)row * a.ldl;
         const bool no_eos = pos < a.min_len;
@@ -291,7 +294,7 @@ __global__ __launch_bounds__(NT) void sample_select_kernel(SampleArgs a) {
             a.slots.pos[row] = pos;
             if (pos < a.max_len) a.out_ids[(size_t)seq * a.max_len + pos] = tok;
             if (a.token_scores && pos < a.max_len) a.token_scores[(size_t)seq * a.ts_ld + pos - 1] = score;
-            if (tok == (int64_t)a.eos || pos + 1 >= a.max_len) {
+            if ((!forced && tok == (int64_t)a.eos) || pos + 1 >= a.max_len) {      // (a forced EOS does not end the row)
                 a.unfinished[row] = 0;
                 a.slots.img[row] = -1;
                 a.slots.out_len[seq] = pos + 1 < a.max_len ? pos + 1 : a.max_len;
@@ -329,6 +332,13 @@ bool sample_select_supported(int V) { return V >= 1 && V <= 4096 * 9; }
 
 void sample_select(const SampleArgs& a, mgStream_t stream) {
     const size_t lds = (256 * SS_COPIES + 16 + 2) * sizeof(u64) + 32 * sizeof(float) + 16 * sizeof(int);
+    if (a.slots.pos && a.con.cls) {
+        const size_t ldc = lds + (size_t)a.con.n_classes * sizeof(int);
+        if (a.V <= 4096) MG_LAUNCH((sample_select_kernel<1, 1024, true, true>), dim3(a.rows), dim3(1024), ldc, stream, a);
+        else if (a.V <= 4096 * 3) MG_LAUNCH((sample_select_kernel<3, 1024, true, true>), dim3(a.rows), dim3(1024), ldc, stream, a);
+        else MG_LAUNCH((sample_select_kernel<18, 512, true, true>), dim3(a.rows), dim3(512), ldc, stream, a);
+        return;
+    }
     if (a.slots.pos) {
         if (a.V <= 4096) MG_LAUNCH((sample_select_kernel<1, 1024, true>), dim3(a.rows), dim3(1024), lds, stream, a);
         else if (a.V <= 4096 * 3) MG_LAUNCH((sample_select_kernel<3, 1024, true>), dim3(a.rows), dim3(1024), lds, stream, a);

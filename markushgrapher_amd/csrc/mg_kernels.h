@@ -411,6 +411,16 @@ struct SlotTable {
     const int64_t* first_tok;   // [N], null = start_id
     int n_stop, stop[4], max_len;
     int nsamp = 1;     // sequences per image (greedy, beam and OCR queues: 1)
+    // greedy / sampled queue under a decoder prompt and / or a constraint (mg_generate_stream_constrained), all null / 0 otherwise; only
+    // slot_refill reads them: a slot handed sequence i is fed the first prompt token of image i / nsamp (written to column 0 of q_out_ids
+    // too) and starts in that image's start state.  The selection kernels take the same prompt and constraint in their own arguments.
+    const int64_t* q_prompt_ids = nullptr;   // [N][q_prompt_ld]; an id outside [0, q_V) becomes 0 and is counted in *q_bad
+    int q_prompt_ld = 0, q_V = 0;
+    int* q_bad = nullptr;                    // nullable
+    int64_t* q_out_ids = nullptr;            // [N * nsamp][q_out_ld], nullable
+    int q_out_ld = 0;
+    const int* q_con_start = nullptr;        // [N] start state per image
+    int* q_con_state = nullptr;              // [slots]
 };
 // Decoder prompt of the batch decode loops (mg_generate_prompted): while the column a row writes is below its prompt length, the
 // selection writes the prompt's token there instead of its own choice - the row stays unfinished whatever the token is (a forced EOS
@@ -420,12 +430,13 @@ struct DecPrompt {
     const int* len;          // [owners] forced columns of the owner's rows, 1 <= len <= ld
     int ld;
     int group;               // rows per owner: row r takes the prompt of owner r / group (samples of an image; 0 / 1: one prompt per row)
+                             // (queue forms: not used - the owner is the image of the sequence in the slot, prompt_forced_owner)
     int* bad;                // nullable
 };
-// -> true: column `col` of `row` is forced, tok = its (checked) token
-MG_DEV bool prompt_forced(const DecPrompt& p, int row, int col, int V, int64_t& tok) {
+// -> true: column `col` of owner `o` is forced, tok = its (checked) token.  The queue forms resolve the owner themselves (the image in
+// the row's slot - of a LIVE row only: an idle slot holds image -1)
+MG_DEV bool prompt_forced_owner(const DecPrompt& p, int o, int col, int V, int64_t& tok) {
     if (!p.ids) return false;
-    const int o = p.group > 1 ? row / p.group : row;
     if (col >= p.len[o]) return false;
     int64_t t = p.ids[(size_t)o * p.ld + col];
     if (t < 0 || t >= (int64_t)V) {
@@ -435,11 +446,19 @@ MG_DEV bool prompt_forced(const DecPrompt& p, int row, int col, int V, int64_t& 
     tok = t;
     return true;
 }
+// batch forms: the owner of row r is r / group
+MG_DEV bool prompt_forced(const DecPrompt& p, int row, int col, int V, int64_t& tok) {
+    return prompt_forced_owner(p, p.group > 1 ? row / p.group : row, col, V, tok);
+}
 // Constraint of the batch decode loops (mg_generate_constrained): a finite automaton over token classes.  Row r is in state[r]; a token
 // t is allowed there iff table[state[r]][cls[t]] >= 0, and that entry is the row's next state.  The selection kernels mask the
 // disallowed tokens exactly as MinLength masks EOS and advance the state with the token they emit; a forced prompt column and a finished
 // row leave the state alone.  The last state is the sink (EOS only).  A live row whose allowed set is empty (MinLength included) emits
 // EOS, ends, moves to the sink, scores 0.0, draws nothing and adds one to *empty.  cls == null: no constraint.
+// Greedy / sampled queue forms (slot table): state is [slots] - the state of the sequence in the slot.  slot_refill sets it to the start
+// state of the sequence's image when it hands the slot over; a row that ends leaves (there is no "finished row keeps its state").  Every
+// entry is a valid state at all times (zeroed at call start), since the greedy kernel stages state[row]'s table row before it knows
+// whether the row is live.
 struct DecConstraint {
     const uint16_t* cls;     // [ldl] class of every token, padded to the logits' row stride (read with the logits' vector pattern)
     const int* table;        // [n_states][n_classes] next state, -1: not allowed
@@ -485,8 +504,8 @@ struct ArgmaxArgs {
     // fused form needs the lm_head partials made with TopOut::lse = 1
     float* token_scores;
     int ts_ld;               // columns per row of token_scores (max_len - 1)
-    DecPrompt prompt;        // batch forms only (slots.pos == null); ids null: none
-    DecConstraint con;       // batch form of greedy_select only (no slot table, no fused tail); cls null: none
+    DecPrompt prompt;        // ids null: none.  Queue form (greedy_select only): one prompt per image, the owner of a live row is slots.img[row] / slots.nsamp
+    DecConstraint con;       // greedy_select only (batch and queue forms; no fused tail); cls null: none
 };
 void greedy_select(const ArgmaxArgs& a, mgStream_t stream);
 void greedy_select_fused(const ArgmaxArgs& a, mgStream_t stream);
@@ -516,8 +535,8 @@ struct SampleArgs {
     float* token_scores;     // nullable, [rows][ts_ld]: log-probability of the drawn token under the warped distribution, column pos - 1
     int ts_ld;
     SlotTable slots;         // continuous decoding (slots.pos == null: batch form)
-    DecPrompt prompt;        // batch form only; a forced row makes no draw
-    DecConstraint con;       // batch form only; cls null: none.  The mask is applied where MinLength's is: before temperature, top-k, top-p
+    DecPrompt prompt;        // a forced row makes no draw.  Queue form: one prompt per image, shared by its samples (owner = slots.img[row] / slots.nsamp)
+    DecConstraint con;       // cls null: none.  The mask is applied where MinLength's is: before temperature, top-k, top-p
 };
 bool sample_select_supported(int V);     // the row is held in registers: V <= 36 864
 void sample_select(const SampleArgs& a, mgStream_t stream);
@@ -540,7 +559,8 @@ void slot_refill(const SlotTable& s, int64_t* next_ids, int* unfinished, int row
 // beam search on the device (k_beam.hip; restates stock generation/utils.py:3208-3525)
 // queue form (continuous beam decoder): per ROW position of the token fed to the step and live flag - the K rows of an image slot
 // hold the same values; pos == null: batch form (one position for all images, the batch's continue flag in counters[0])
-struct BeamSlots { const int* pos; const int* live; };
+// img (nullable; needed under a prompt): per row the image in the row's slot, -1 = idle - the owner of the slot's prompt and start state
+struct BeamSlots { const int* pos; const int* live; const int* img = nullptr; };
 size_t beam_state_bytes(int B, int K, int max_len);
 // prompt (nullable; batch form, one owner per image, group ignored): the K rows of image b start holding its prompt (stock writes
 // input_ids into running_sequences and sequences, utils.py:3326-3327), V bounds its ids
@@ -551,7 +571,7 @@ float beam_length_divisor(int cur_len, float length_penalty);
 void beam_step(void* state, const float* logits, int ldl, int V, int B, int K, int max_len, int cur_len, const int* tdev,
                const float* div_table, int eos, int min_len, float length_penalty, int early_stopping, int64_t* next_ids,
                int* beam_idx, int* counters, mgStream_t stream, const BeamSlots* slots = nullptr, const DecPrompt* prompt = nullptr,
-               const DecConstraint* con = nullptr);      // con (batch form): the row top-k masks, the update reorders and advances the K states
+               const DecConstraint* con = nullptr);      // con: the row top-k masks, the update reorders and advances the K states (queue form: of the slot's rows)
 // n-best output of an image's finished hypotheses (best first).  Hypothesis h < num_return of image i is output row i * num_return + h:
 // out_ids [rows][max_len], scores [rows] (sequence scores), and, nullable, beam_indices [rows][max_len - 1] (stock semantics: the flat row
 // image * K + beam each token was chosen from, -1 past the hypothesis' length) and token_scores [rows][max_len - 1] (the processed
@@ -572,7 +592,10 @@ void beam_reorder_anc(int* anc, const int* beam_idx, int rows, int t_written, co
 // [4] queue head, [5] ready, [7] oldest live image)
 void beam_slots_step(void* state, int slots, int K, int max_len, int pad, int eos, int start, int early_stopping, int* pos, int* img, int* pool,
                      int* bpool, int* live, int* assign, int64_t* next_ids, int* anc, int T_cap, int pool_cap, int64_t* out_ids, int* out_len,
-                     float* out_scores, int* ctr, bool end_first, mgStream_t stream, const BeamOut* nbest = nullptr);
+                     float* out_scores, int* ctr, bool end_first, mgStream_t stream, const BeamOut* nbest = nullptr,
+                     // queue under a prompt / constraint (per image of the queue; V bounds the prompt's ids): a newly assigned slot starts as
+                     // beam_init starts image `assign[slot]` - con_state [slots * K], con_start [N]
+                     const DecPrompt* prompt = nullptr, int V = 0, int* con_state = nullptr, const int* con_start = nullptr);
 // physical form: dst[lk][row] = src[lk][beam_idx[row]] for nlk = layers*2 K/V planes of [rows][H][t_cap][64] bf16
 void beam_reorder_copy(const uint16_t* src, uint16_t* dst, const int* beam_idx, int nlk, int rows, int H, int t_cap, int t_used,
                        mgStream_t stream);

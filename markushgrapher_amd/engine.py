@@ -184,6 +184,11 @@ class Engine:
         L.mg_generate_stream_sampled.argtypes = L.mg_generate_stream.argtypes + [C.POINTER(MgSampleOpts)]
         L.mg_generate_stream_beam_scored.argtypes = L.mg_generate_stream_beam.argtypes[:-3] + [C.c_void_p, C.POINTER(C.c_long),
                                                                                                C.POINTER(MgGenOpts)]
+        L.mg_stream_constrained_workspace_bytes.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.POINTER(C.c_size_t)]
+        L.mg_generate_stream_constrained.argtypes = L.mg_generate_stream_scored.argtypes + [C.POINTER(MgSampleOpts), C.POINTER(MgDecoderPrompt),
+                                                                                           C.POINTER(MgConstraint)]
+        L.mg_generate_stream_beam_constrained.argtypes = L.mg_generate_stream_beam_scored.argtypes + [C.POINTER(MgDecoderPrompt),
+                                                                                                     C.POINTER(MgConstraint)]
         L.mg_stream_encoder_mode.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.mg_debug_bucket_table.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int]
         L.mg_debug_decode_capture.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -639,19 +644,46 @@ class Engine:
         res = (self.mem.copy(c["ids"][:, :n]), n, self.mem.copy(c["ts"][:, :n - 1]) if return_scores else None)
         return res + (top2,) if return_top2 else res
 
-    def generate_stream(self, input_ids, bbox, attention_mask, pixel_values, max_length=512, min_length=0, chunk=32, slots=32,
-                        pool_chunks=3, return_scores=False):
-        """Continuous greedy decoding of N images (include/mgrapher.h mg_generate_stream): -> (ids [N, max_length] padded with the pad
-        id, lengths [N] = valid columns, decode steps run).  Row n equals generate()'s row for image n.
-        return_scores: a fourth item, token_scores [N, max_length - 1] (mg_generate_stream_scored: the log-probability of the token in
-        column j + 1 at column j, 0.0 after the image's EOS)."""
-        ids, bb, am, pv, N, L = self._inputs(input_ids, bbox, attention_mask, pixel_values)
+    def _stream_ws(self, chunk, L, slots, pool_chunks, N=0, max_length=0, num_beams=1):
+        """The queue's workspace, grown on demand (N > 0: with the extras of a prompted / constrained queue)."""
         need = C.c_size_t()
-        self._chk(self.lib.mg_stream_workspace_bytes(self.model, chunk, L, slots, pool_chunks, C.byref(need)))
+        if N > 0:
+            self._chk(self.lib.mg_stream_constrained_workspace_bytes(self.model, chunk, L, slots, pool_chunks, num_beams, max_length, N,
+                                                                     C.byref(need)))
+        elif num_beams > 1:
+            self._chk(self.lib.mg_stream_beam_workspace_bytes(self.model, chunk, L, slots, pool_chunks, num_beams, max_length, C.byref(need)))
+        else:
+            self._chk(self.lib.mg_stream_workspace_bytes(self.model, chunk, L, slots, pool_chunks, C.byref(need)))
         if getattr(self, "_sws_bytes", 0) < need.value:
             self._sws = None
             self._sws = self.mem.empty((need.value,), np.uint8)
             self._sws_bytes = need.value
+
+    def _chk_queue(self, rc, outputs):
+        """_chk for a prompted / constrained queue call: MG_E_INPUT (an empty allowed set, a prompt id outside the vocabulary) comes after
+        the call has completed, so the error carries the outputs (`outputs()` -> what the call would have returned)."""
+        try:
+            self._chk(rc)
+        except MgError as e:
+            if rc == -8:
+                e.outputs = outputs()
+            raise
+
+    def generate_stream(self, input_ids, bbox, attention_mask, pixel_values, max_length=512, min_length=0, chunk=32, slots=32,
+                        pool_chunks=3, return_scores=False, decoder_prompt=None, decoder_prompt_len=None, constraint=None,
+                        constraint_start=None):
+        """Continuous greedy decoding of N images (include/mgrapher.h mg_generate_stream): -> (ids [N, max_length] padded with the pad
+        id, lengths [N] = valid columns, decode steps run).  Row n equals generate()'s row for image n.
+        return_scores: a fourth item, token_scores [N, max_length - 1] (mg_generate_stream_scored: the log-probability of the token in
+        column j + 1 at column j, 0.0 after the image's EOS).
+        decoder_prompt [N, P] / decoder_prompt_len [N], constraint (a TokenAutomaton) / constraint_start [N]: per image of the queue, as
+        generate() takes them per image of a batch (mg_generate_stream_constrained); row n then equals generate() on image n alone with its
+        prompt and start state.  An MgError of code -8 (an empty allowed set, a bad prompt id) carries the completed results in `.outputs`."""
+        ids, bb, am, pv, N, L = self._inputs(input_ids, bbox, attention_mask, pixel_values)
+        prompt = self._prompt(decoder_prompt, decoder_prompt_len, N)
+        con = self._constraint(constraint, constraint_start, N)
+        extra = prompt is not None or con is not None
+        self._stream_ws(chunk, L, slots, pool_chunks, N if extra else 0, max_length)
         okey = ("stream", N, max_length)
         out = self._gen_out.get(okey)
         if out is None:
@@ -660,20 +692,31 @@ class Engine:
         args = (self.model, self.mem.stream(), self.mem.ptr(self._sws), self._sws_bytes, self.mem.ptr(ids), self.mem.ptr(bb),
                 self.mem.ptr(am) if am is not None else None, self.mem.ptr(pv), N, L, chunk, slots, pool_chunks, max_length, min_length,
                 self.mem.ptr(out[0]), self.mem.ptr(out[1]), C.byref(steps))
-        if not return_scores:
+        if not return_scores and not extra:
             self._chk(self.lib.mg_generate_stream(*args))
             return self.mem.copy(out[0]), self.mem.copy(out[1]), int(steps.value)
         opts, ts, _, _ = self._scored_out("stream", N, max_length, False)
+        if extra:
+            def results():
+                res = (self.mem.copy(out[0]), self.mem.copy(out[1]), int(steps.value))
+                return res + (self.mem.copy(ts),) if return_scores else res
+            self._chk_queue(self.lib.mg_generate_stream_constrained(*args, C.byref(opts) if return_scores else None, None,
+                                                                    C.byref(prompt) if prompt is not None else None,
+                                                                    C.byref(con) if con is not None else None), results)
+            return results()
         self._chk(self.lib.mg_generate_stream_scored(*args, C.byref(opts)))
         return self.mem.copy(out[0]), self.mem.copy(out[1]), int(steps.value), self.mem.copy(ts)
 
     def generate_stream_sampled(self, input_ids, bbox, attention_mask, pixel_values, max_length=512, min_length=0, temperature=1.0, top_k=0,
-                                top_p=1.0, seed=0, num_return=1, stream_ids=None, chunk=32, slots=32, pool_chunks=3, return_scores=False):
+                                top_p=1.0, seed=0, num_return=1, stream_ids=None, chunk=32, slots=32, pool_chunks=3, return_scores=False,
+                                decoder_prompt=None, decoder_prompt_len=None, constraint=None, constraint_start=None):
         """The greedy queue under sampling (include/mgrapher.h mg_generate_stream_sampled): N images with num_return samples each are a
         queue of N * num_return sequences on `slots` decode rows -> (ids [N * num_return, max_length] padded with the pad id, lengths
         [N * num_return], decode steps run[, token_scores [N * num_return, max_length - 1]]).  Row n * num_return + j is sample j of image
         n and equals generate_sampled() on image n alone with stream id n * num_return + j (stream_ids [N * num_return] names other ids),
-        cut at its length.  One encoder pass and one pool entry per image."""
+        cut at its length.  One encoder pass and one pool entry per image.
+        decoder_prompt [N, P] / decoder_prompt_len [N], constraint / constraint_start [N]: per IMAGE, shared by its samples, as
+        generate_sampled() takes them (mg_generate_stream_constrained); `.outputs` of an MgError of code -8 as in generate_stream."""
         ids, bb, am, pv, N, L = self._inputs(input_ids, bbox, attention_mask, pixel_values)
         nr = int(num_return)
         if nr < 1:
@@ -685,12 +728,10 @@ class Engine:
         if not 0.0 < float(top_p) <= 1.0:
             raise ValueError(f"top_p must be in (0, 1], got {top_p}")
         R = N * nr
-        need = C.c_size_t()
-        self._chk(self.lib.mg_stream_workspace_bytes(self.model, chunk, L, slots, pool_chunks, C.byref(need)))
-        if getattr(self, "_sws_bytes", 0) < need.value:
-            self._sws = None
-            self._sws = self.mem.empty((need.value,), np.uint8)
-            self._sws_bytes = need.value
+        prompt = self._prompt(decoder_prompt, decoder_prompt_len, N)
+        con = self._constraint(constraint, constraint_start, N)
+        extra = prompt is not None or con is not None
+        self._stream_ws(chunk, L, slots, pool_chunks, N if extra else 0, max_length)
         # persistent output / stream-id buffers: the captured decode step holds their addresses
         okey = ("stream-sampled", R, max_length)
         c = self._gen_out.get(okey)
@@ -709,30 +750,38 @@ class Engine:
                             self.mem.ptr(sid).value if sid is not None else None, nr,
                             self.mem.ptr(c["ts"]).value if return_scores else None)
         steps = C.c_long(0)
-        self._chk(self.lib.mg_generate_stream_sampled(
-            self.model, self.mem.stream(), self.mem.ptr(self._sws), self._sws_bytes, self.mem.ptr(ids), self.mem.ptr(bb),
-            self.mem.ptr(am) if am is not None else None, self.mem.ptr(pv), N, L, chunk, slots, pool_chunks, max_length, min_length,
-            self.mem.ptr(c["ids"]), self.mem.ptr(c["len"]), C.byref(steps), C.byref(opts)))
-        res = (self.mem.copy(c["ids"]), self.mem.copy(c["len"]), int(steps.value))
-        return res + (self.mem.copy(c["ts"]),) if return_scores else res
+        args = (self.model, self.mem.stream(), self.mem.ptr(self._sws), self._sws_bytes, self.mem.ptr(ids), self.mem.ptr(bb),
+                self.mem.ptr(am) if am is not None else None, self.mem.ptr(pv), N, L, chunk, slots, pool_chunks, max_length, min_length,
+                self.mem.ptr(c["ids"]), self.mem.ptr(c["len"]), C.byref(steps))
+
+        def results():
+            res = (self.mem.copy(c["ids"]), self.mem.copy(c["len"]), int(steps.value))
+            return res + (self.mem.copy(c["ts"]),) if return_scores else res
+        if extra:
+            self._chk_queue(self.lib.mg_generate_stream_constrained(*args, None, C.byref(opts), C.byref(prompt) if prompt is not None else None,
+                                                                    C.byref(con) if con is not None else None), results)
+        else:
+            self._chk(self.lib.mg_generate_stream_sampled(*args, C.byref(opts)))
+        return results()
 
     def generate_stream_beam(self, input_ids, bbox, attention_mask, pixel_values, num_beams=5, max_length=512, min_length=0,
-                             length_penalty=1.0, early_stopping=False, chunk=32, slots=32, pool_chunks=3, num_return=1, return_scores=False):
+                             length_penalty=1.0, early_stopping=False, chunk=32, slots=32, pool_chunks=3, num_return=1, return_scores=False,
+                             decoder_prompt=None, decoder_prompt_len=None, constraint=None, constraint_start=None):
         """Continuous BEAM-SEARCH decoding of N images (include/mgrapher.h mg_generate_stream_beam): `slots` image slots of num_beams
         rows -> (ids [N, max_length] = best hypothesis per image, lengths [N], scores [N], decode steps run).  Row n equals
         generate(num_beams=...)'s result for image n.
         num_return > 1: the n-best list - ids [N * num_return, max_length] and scores [N * num_return] (hypotheses of an image consecutive,
         best first), lengths [N] = the longest returned hypothesis' columns.  return_scores: a fifth item, {"token_scores", "beam_indices"}
-        [N * num_return, max_length - 1] (mg_generate_stream_beam_scored)."""
+        [N * num_return, max_length - 1] (mg_generate_stream_beam_scored).
+        decoder_prompt [N, P] / decoder_prompt_len [N], constraint / constraint_start [N]: per image of the queue, as generate(num_beams=...)
+        takes them per image of a batch (mg_generate_stream_beam_constrained)."""
         ids, bb, am, pv, N, L = self._inputs(input_ids, bbox, attention_mask, pixel_values)
         if slots * num_beams > self.MAX_LIVE_ROWS:
             raise MgError(f"generate_stream_beam: slots * num_beams = {slots * num_beams} rows exceed the supported {self.MAX_LIVE_ROWS}")
-        need = C.c_size_t()
-        self._chk(self.lib.mg_stream_beam_workspace_bytes(self.model, chunk, L, slots, pool_chunks, num_beams, max_length, C.byref(need)))
-        if getattr(self, "_sws_bytes", 0) < need.value:
-            self._sws = None
-            self._sws = self.mem.empty((need.value,), np.uint8)
-            self._sws_bytes = need.value
+        prompt = self._prompt(decoder_prompt, decoder_prompt_len, N)
+        con = self._constraint(constraint, constraint_start, N)
+        extra = prompt is not None or con is not None
+        self._stream_ws(chunk, L, slots, pool_chunks, N if extra else 0, max_length, num_beams)
         nr = int(num_return)
         if not 1 <= nr <= num_beams:
             raise ValueError(f"num_return must be in [1, num_beams = {num_beams}], got {nr}")
@@ -742,16 +791,22 @@ class Engine:
             out = self._gen_out[okey] = (self.mem.empty((N * nr, max_length), np.int64), self.mem.empty((N,), np.int32),
                                          self.mem.empty((N * nr,), np.float32))
         steps = C.c_long(0)
-        if nr > 1 or return_scores:
+        if nr > 1 or return_scores or extra:
             opts, ts, ss, bi = self._scored_out("stream-beam", N * nr, max_length, True)
             opts.num_return = nr
             if not return_scores:
                 opts.token_scores = opts.beam_indices = None
-            self._chk(self.lib.mg_generate_stream_beam_scored(
-                self.model, self.mem.stream(), self.mem.ptr(self._sws), self._sws_bytes, self.mem.ptr(ids), self.mem.ptr(bb),
-                self.mem.ptr(am) if am is not None else None, self.mem.ptr(pv), N, L, chunk, slots, pool_chunks, num_beams, max_length,
-                min_length, C.c_float(length_penalty), 1 if early_stopping else 0, self.mem.ptr(out[0]), self.mem.ptr(out[1]), C.byref(steps),
-                C.byref(opts)))
+            args = (self.model, self.mem.stream(), self.mem.ptr(self._sws), self._sws_bytes, self.mem.ptr(ids), self.mem.ptr(bb),
+                    self.mem.ptr(am) if am is not None else None, self.mem.ptr(pv), N, L, chunk, slots, pool_chunks, num_beams, max_length,
+                    min_length, C.c_float(length_penalty), 1 if early_stopping else 0, self.mem.ptr(out[0]), self.mem.ptr(out[1]), C.byref(steps),
+                    C.byref(opts))
+            if extra:
+                self._chk(self.lib.mg_generate_stream_beam_constrained(*args, C.byref(prompt) if prompt is not None else None,
+                                                                       C.byref(con) if con is not None else None))
+                if nr == 1 and not return_scores:
+                    return self.mem.copy(out[0]), self.mem.copy(out[1]), self.mem.copy(ss), int(steps.value)
+            else:
+                self._chk(self.lib.mg_generate_stream_beam_scored(*args))
             res = (self.mem.copy(out[0]), self.mem.copy(out[1]), self.mem.copy(ss), int(steps.value))
             if return_scores:
                 res += ({"token_scores": self.mem.copy(ts), "beam_indices": self.mem.copy(bi)},)
