@@ -14,6 +14,10 @@
  *                       replace   torch.argmax(model(**sample).logits, dim=2) against the labels, and the loss / the
  *                                 log-probability of given sequences, without the logits
  *                                 markushgrapher/core/trainers/curriculumTrainer.py:654-672
+ *   mg_encode + mg_decoder_attribute
+ *                       replace   the cross_attentions of model(**sample, output_attentions=True), averaged over heads and layers,
+ *                                 without the per-layer [B][H][T][S] tensors (config.output_attentions = True,
+ *                                 markushgrapher/core/common/begin.py:121)
  *   mg_create / mg_load_tensor / mg_finalize
  *                       replace   MarkushgrapherForConditionalGeneration.from_pretrained(...).to(device)
  *                                 /root/reference/markushgrapher/core/common/begin.py:128-133
@@ -119,6 +123,33 @@ int mg_score_workspace_bytes(const mg_model* m, int B, int L, int T, int M_e1, s
 int mg_decoder_score(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* decoder_input_ids,
                      const uint8_t* decoder_attention_mask, const int64_t* targets, int B, int T, float* token_logprobs,
                      int64_t* argmax_ids, float* argmax_logprobs);
+
+/* Attribution of given sequences: WHERE in the page each decoder position looked.  mg_decoder_forward's stack with one more launch per
+ * selected layer (csrc/k_attrib.hip) that forms the cross-attention softmax from the bf16 Q / K operands of that layer's cross-attention
+ * launch and reduces it on the chip - the [B][H][T][S] probabilities per layer that `output_attentions=True` materialises
+ * (markushgrapher/core/common/begin.py:121 sets it on every model) are never stored.
+ *   p[l][h][b][t][k] = softmax over the ATTENDED keys of (q . k): no scale, no bias (stock UDOP cross-attention), in fp32 - exp(s - max) / sum,
+ *                      not the bf16-rounded weights of the P.V product
+ *   map[b][t][k]     = 1 / (n_layers * H) * sum_{l = layer_first .. layer_last} sum_h p[l][h][b][t][k]      (ascending l, then ascending h)
+ * map [B][T][M_e1 + L + P] fp32, key axis = [e1 tokens | text slots | visual slots]: mg_encode's enc_out / enc_mask order preceded by the
+ * OCSR-branch tokens when the preceding mg_encode had them.  Keys with enc_mask == 0 are exactly 0.0; rows with decoder_attention_mask == 0
+ * are exactly 0.0; every other row sums to 1 within fp32 rounding.  opts NULL: all decoder layers.
+ * Requires a preceding mg_encode on the same workspace and may be called several times after it.  SYNCHRONISES.  Deterministic: an
+ * image's map does not depend on B, on the other images, or on T beyond its own row.
+ * Errors: MG_E_ARG layers outside [0, num_decoder_layers) or layer_first > layer_last; MG_E_SHAPE T outside [1, max_decode_len rounded up
+ * to 64]; MG_E_STATE no preceding mg_encode; MG_E_WORKSPACE; MG_E_INPUT token ids outside the vocabulary, or an image without a single
+ * attended key; MG_E_UNSUPPORTED more than 1536 keys per image (L + P + M_e1 rounded up to 64: the kernel keeps a query tile's head sums
+ * over all keys in registers).
+ * WORKSPACE: mg_attribute_workspace_bytes = mg_workspace_bytes(B, L, 1, 0, T, M_e1) plus the running sums behind it (4 bytes per query
+ * and key, both rounded up to 32, plus a 256-byte header); such a workspace also serves mg_encode / mg_decoder_forward of the same B, L, T.
+ * NOT built: maps from inside mg_generate* or the queue forms; self-attention and encoder attention maps; per-head or per-layer outputs;
+ * rollout or gradient-based attribution; the ChemicalOCR stage. */
+typedef struct mg_attr_opts {
+    int layer_first, layer_last;     /* inclusive range of decoder layers */
+} mg_attr_opts;
+int mg_attribute_workspace_bytes(const mg_model* m, int B, int L, int T, int M_e1, size_t* out_bytes);
+int mg_decoder_attribute(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* decoder_input_ids,
+                         const uint8_t* decoder_attention_mask, int B, int T, const mg_attr_opts* opts, float* map /* [B][T][M_e1 + L + P] */);
 
 /* generate(): encoder once, then KV-cached decode.  num_beams == 1: greedy (stock generation/utils.py:2783-2975);
  * num_beams > 1: beam search (utils.py:3208-3525, beams_to_keep = 2*num_beams, length_penalty, early_stopping 0/1).
@@ -590,6 +621,16 @@ int mgk_attention(void* stream, int mode, const void* Q, const void* K, const vo
                   int Sq, int Sk, int Sq_cap, int Sk_cap, const uint8_t* kmask, const float* tab1, int tab1_len,
                   const float* tabh, const float* tabv, const double* cx, const double* cy, const int* bk1, const int* bkhv,
                   void* bidx_scratch);
+/* One layer's launch of the attribution kernel (csrc/k_attrib.hip), then - map non-null - the gather into map [B][Sq][M_e1 + L + P].
+ * Q [B][H][Sq_cap][64], K [B][H][Sk_cap][64] as mgk_attention's (HF_PK_ROWS); keys per image Sk = M_pad + L + P <= min(Sk_cap, 1536):
+ * [e1 slots (M_pad, a multiple of 64, the first M_e1 real) | workspace rows of the encoder]; kmask [B][Sk_cap] (nullable).  The head-summed
+ * fp32 softmax is stored to scratch (accumulate = 0) or added to it (1), times `scale`.  Column M_e1 + s of the map is encoder output
+ * position s in [text L | patches P] order (text_len [B] nullable: image b's workspace rows are [text text_len[b] | patches | text padding]);
+ * rows with qmask[b][q] == 0 (qmask [B][Sq], nullable) are 0.0.  scratch: mgk_xattn_map_scratch_bytes(B, Sq, Sk), MG_E_WORKSPACE if smaller. */
+size_t mgk_xattn_map_scratch_bytes(int B, int Sq, int Sk);
+int mgk_xattn_map(void* stream, const void* Q, const void* K, int B, int H, int Sq, int Sq_cap, int Sk_cap, const uint8_t* kmask, int accumulate,
+                  float scale, void* scratch, size_t scratch_bytes, int M_e1, int M_pad, int L, int P, const int* text_len, const uint8_t* qmask,
+                  float* map);
 /* mgk_attention(mode 0) with the skip lists mg_encode uses: 64-key stages / 128-query blocks without an attended position
  * are not visited (kst_scratch: B*(1+S_cap/64) ints, qbv_scratch: B*ceil(S_cap/128) bytes). */
 int mgk_attention_enc_skip(void* stream, const void* Q, const void* K, const void* Vt, void* ctx_pk, int B, int H, int S, int S_cap,

@@ -549,6 +549,24 @@ int mgk_score(void* stream, const void* X_pk, const void* W_pk, int M, int N, in
     return MG_OK;
 }
 
+// Cross-attention attribution (xattn_map + xattn_map_gather, k_attrib.hip): one call = one layer's launch, then the gather into `map`
+// [B][Sq][M_e1 + L + P] when map is non-null.  Sk = M_pad + L + P keys per image; scratch keeps the running sums between calls.
+size_t mgk_xattn_map_scratch_bytes(int B, int Sq, int Sk) { return (B < 1 || Sq < 1 || Sk < 1) ? 0 : xattn_map_scratch_bytes(B, Sq, Sk); }
+int mgk_xattn_map(void* stream, const void* Q, const void* K, int B, int H, int Sq, int Sq_cap, int Sk_cap, const uint8_t* kmask, int accumulate,
+                  float scale, void* scratch, size_t scratch_bytes, int M_e1, int M_pad, int L, int P, const int* text_len, const uint8_t* qmask,
+                  float* map) {
+    if (!Q || !K || !scratch) return MG_E_ARG;
+    if (B < 1 || H < 1 || Sq < 1 || M_e1 < 0 || M_pad < M_e1 || (M_pad & 63) || L < 0 || P < 0) return MG_E_SHAPE;
+    const int Sk = M_pad + L + P;
+    if (Sk < 1 || (Sq_cap & 31) || (Sk_cap & 63) || Sk > Sk_cap || Sq > Sq_cap) return MG_E_SHAPE;
+    if (!xattn_map_supported(Sk)) return MG_E_UNSUPPORTED;
+    if (scratch_bytes < xattn_map_scratch_bytes(B, Sq, Sk)) return MG_E_WORKSPACE;
+    const XattnMapArgs a{(const uint16_t*)Q, (const uint16_t*)K, B, H, Sq, Sk, Sq_cap, Sk_cap, kmask, accumulate, scale, (float*)scratch};
+    if (xattn_map(a, (mgStream_t)stream) != 0) return MG_E_UNSUPPORTED;
+    if (map) xattn_map_gather(XattnGatherArgs{(const float*)scratch, map, B, Sq, Sk, M_e1, M_pad, L, P, text_len, qmask, Sq}, (mgStream_t)stream);
+    return MG_OK;
+}
+
 // mgk_lm_head_top as the decode step launches it: the deferred row scale of the final norm and up to four stop tokens (host array, -1 = unused);
 // ptop null: the plain projection (the unfused tail's launch)
 int mgk_lm_head_step(void* stream, const void* X_pk, const void* W_pk, float* P, int M, int N, int K, int ldp, const float* rs_part, int rs_nparts,

@@ -267,6 +267,12 @@ __global__ __launch_bounds__(256) void pad_dec_inputs_kernel(const int64_t* ids,
         dst_row[i] = in ? b * T + t : -1;
     }
 }
+// images without a single attended cross-attention key (kmask [B][cap], keys < Sk): counted in *err.  One workgroup per image.
+__global__ __launch_bounds__(64) void count_keyless_images_kernel(const uint8_t* kmask, int Sk, int cap, int* err) {
+    int any = 0;
+    for (int i = threadIdx.x; i < Sk; i += blockDim.x) any |= kmask[(size_t)blockIdx.x * cap + i] != 0;
+    if (!wave_any(any != 0) && threadIdx.x == 0) atomicAdd(err, 1);
+}
 // Output position s of image b (the documented [text L | patches P] order) -> row of the workspace.  With per-image padding
 // semantics (text_len[b] = Lb < L) the workspace holds [text Lb | patches P | text padding L - Lb].
 MG_DEV size_t enc_src_row(int s, int L, int P, const int* text_len, int b) {
@@ -1314,9 +1320,16 @@ int mg_encode(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_
 }
 
 // Teacher-forced decoder stack up to and including the final norm: leaves the B*T real positions, normalised and packed, in w.tf_xc
-// (the operand of the lm_head).  Shared by mg_decoder_forward (logits) and mg_decoder_score (fused log-probabilities).
+// (the operand of the lm_head).  Shared by mg_decoder_forward (logits), mg_decoder_score (fused log-probabilities) and
+// mg_decoder_attribute.  attr (nullable; null = the same launches in the same order as without the argument): after the cross-Q and
+// cross-K projections of every layer in [layer_first, layer_last] one xattn_map launch adds that layer's head-summed softmax to
+// attr->scratch - stored by the first selected layer, scaled by 1 / (layers * H) in the last one's launch.
+struct AttrHook {
+    int layer_first, layer_last;
+    float* scratch;
+};
 static void decoder_stack(mg_model* m, mgStream_t st, const Ws& w, const int64_t* decoder_input_ids, const uint8_t* decoder_attention_mask,
-                          int B, int T) {
+                          int B, int T, const AttrHook* attr = nullptr) {
     const int d = m->d, H = m->H, inner = m->inner;
     const int T_cap = round_up(T, 64), MT = B * T_cap, S = m->st_S, S_cap = m->st_Scap, M = B * S_cap;
     const int M64 = m->st_M > 0 ? round_up(m->st_M, 64) : 0, Sx_cap = S_cap + M64;
@@ -1352,6 +1365,11 @@ static void decoder_stack(mg_model* m, mgStream_t st, const Ws& w, const int64_t
         set_heads(kv, H, S_cap, Sx_cap, w.tf_xk, HF_PK_ROWS, w.tf_xvt, HF_PK_T, nullptr, HF_NONE);
         kv.heads.s_off = M64;
         gemm(kv, EPI_HEADS, st);
+        if (attr && (int)li >= attr->layer_first && (int)li <= attr->layer_last) {
+            XattnMapArgs xm{w.tf_q, w.tf_xk, B, H, T, M64 + S, T_cap, Sx_cap, M64 ? w.xmask : w.mask, (int)li > attr->layer_first ? 1 : 0,
+                            (int)li == attr->layer_last ? 1.0f / (float)((attr->layer_last - attr->layer_first + 1) * H) : 1.0f, attr->scratch};
+            (void)xattn_map(xm, st);                     // (the key count was checked by the caller: xattn_map_supported)
+        }
         AttnArgs x{};
         x.Q = w.tf_q; x.K = w.tf_xk; x.Vt = w.tf_xvt; x.ctx = w.tf_ctx; x.B = B; x.H = H; x.Sq = T; x.Sk = M64 + S;
         x.Sq_cap = T_cap; x.Sk_cap = Sx_cap; x.mode = ATT_CROSS; x.kmask = M64 ? w.xmask : w.mask;
@@ -1430,6 +1448,62 @@ int mg_decoder_score(mg_model* m, void* stream, void* ws, size_t ws_bytes, const
     if (rc != MG_OK) return rc;
     if (bad_ids != 0) return fail(MG_E_INPUT, "mg_decoder_score: %d token ids outside [0, vocab)", bad_ids);
     if (bad_targets != 0) return fail(MG_E_INPUT, "mg_decoder_score: %d targets outside [ignored (< 0), vocab)", bad_targets);
+    return MG_OK;
+}
+
+// the map scratch sits behind the teacher-forced layout (as the score kernel's): a 256-byte header (error word), then the running sums in
+// the kernel's accumulator order
+constexpr size_t ATTR_HEADER = 256;
+static size_t attr_ws_total(const mg_model* m, const Ws& w, int B, int L, int T, int M_e1) {
+    const int M64 = M_e1 > 0 ? round_up(M_e1, 64) : 0;
+    return align_up(align_up(w.total, 256) + ATTR_HEADER + xattn_map_scratch_bytes(B, T, M64 + L + m->P), 256);
+}
+
+int mg_attribute_workspace_bytes(const mg_model* m, int B, int L, int T, int M_e1, size_t* out_bytes) {
+    if (!m || !out_bytes || B < 1 || L < 1 || T < 1 || M_e1 < 0) return fail(MG_E_ARG, "mg_attribute_workspace_bytes: bad argument");
+    Ws w;
+    if (M_e1 == 0) M_e1 = m->e1_M;
+    carve(m, nullptr, B, L, 1, 0, T, M_e1, &w);
+    *out_bytes = attr_ws_total(m, w, B, L, T, M_e1);
+    return MG_OK;
+}
+
+int mg_decoder_attribute(mg_model* m, void* stream, void* ws, size_t ws_bytes, const int64_t* decoder_input_ids,
+                         const uint8_t* decoder_attention_mask, int B, int T, const mg_attr_opts* opts, float* map) {
+    entry_drain();
+    if (!m || !ws || !decoder_input_ids || !map) return fail(MG_E_ARG, "mg_decoder_attribute: null argument");
+    const int NL = (int)m->dec.size();
+    const int l0 = opts ? opts->layer_first : 0, l1 = opts ? opts->layer_last : NL - 1;
+    if (l0 < 0 || l1 >= NL || l0 > l1) return fail(MG_E_ARG, "mg_decoder_attribute: layers [%d, %d] outside [0, %d) or empty", l0, l1, NL);
+    MG_ONE_CALL(m, "mg_decoder_attribute");
+    if (m->st_ws != ws || m->st_B != B) return fail(MG_E_STATE, "mg_decoder_attribute: run mg_encode on this workspace/batch first");
+    if (T < 1 || T > m->T_cap) return fail(MG_E_SHAPE, "mg_decoder_attribute: T must be in [1, %d]", m->T_cap);
+    mgStream_t st = (mgStream_t)stream;
+    Ws w;
+    carve(m, (char*)ws, B, m->st_L, 1, 0, T, m->st_M, &w);
+    const int L = m->st_L, S = m->st_S, M_e1 = m->st_M, M64 = M_e1 > 0 ? round_up(M_e1, 64) : 0, Sx_cap = m->st_Scap + M64;
+    if (!xattn_map_supported(M64 + S))
+        return fail(MG_E_UNSUPPORTED, "mg_decoder_attribute: %d cross-attention keys per image, the map kernel holds at most 1536", M64 + S);
+    const size_t total = attr_ws_total(m, w, B, L, T, M_e1);
+    if (total > ws_bytes) return fail(MG_E_WORKSPACE, "mg_decoder_attribute: workspace too small (%zu < %zu): size it with mg_attribute_workspace_bytes", ws_bytes, total);
+    char* head = (char*)ws + align_up(w.total, 256);
+    int* err = (int*)head;
+    const AttrHook hook{l0, l1, (float*)(head + ATTR_HEADER)};
+    const uint8_t* kmask = M64 ? w.xmask : w.mask;
+    mg_memset_async(err, 0, ATTR_HEADER, st);
+    MG_LAUNCH(count_keyless_images_kernel, dim3(B), dim3(64), 0, st, kmask, M64 + S, Sx_cap, err);
+    decoder_stack(m, st, w, decoder_input_ids, decoder_attention_mask, B, T, &hook);
+    // rows in the documented [e1 | text | patches] order, through the per-image padding map; rows under a zero decoder mask are 0.0
+    xattn_map_gather(XattnGatherArgs{hook.scratch, map, B, T, M64 + S, M_e1, M64, L, S - L, m->trim_padding ? w.text_len : nullptr, w.tf_mask,
+                                     round_up(T, 64)}, st);
+    int bad_ids = 0, keyless = 0;
+    mg_memcpy_async(&bad_ids, w.counters + 3, sizeof(int), st);
+    mg_memcpy_async(&keyless, err, sizeof(int), st);
+    mg_stream_sync(st);
+    const int rc = check_launch("mg_decoder_attribute");
+    if (rc != MG_OK) return rc;
+    if (bad_ids != 0) return fail(MG_E_INPUT, "mg_decoder_attribute: %d token ids outside [0, vocab)", bad_ids);
+    if (keyless != 0) return fail(MG_E_INPUT, "mg_decoder_attribute: %d images without an attended cross-attention key", keyless);
     return MG_OK;
 }
 

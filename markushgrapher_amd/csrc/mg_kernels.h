@@ -287,7 +287,37 @@ void attn_lists(const uint8_t* kmask, int B, int Sk, int S_cap, int* kst, uint8_
 // live 32-row tiles of a [rows] key mask (rows a multiple of 32, mask 16-byte aligned) -> ascending tile ids + count (GemmArgs::row_tiles)
 void row_tile_list(const uint8_t* kmask, int rows, int* list, int* count, mgStream_t stream);
 void attention(const AttnArgs& a, mgStream_t stream);
-void attention_set_qt(int qt);   // encoder attention: 1 (default) one 32-query tile per wave, 8 waves; 2: two tiles per wave, 4 waves (same bits, measured slower; tests, A/B runs)
+// Cross-attention attribution (k_attrib.hip): the fp32 softmax of Q K^T (no scale, no bias, masked keys excluded) summed over the heads of
+// one layer in registers and added to `scratch`, which is in accumulator order [image][ceil(Sq/32)][ceil(Sk/32)][16][64] fp32
+// (xattn_map_scratch_bytes).  accumulate = 0: the layer's sums are stored (first selected layer); 1: added to what is there.  The stored
+// value is multiplied by `scale` (1 / (layers * H) in the last selected layer's launch, 1 before).  Q / K: HF_PK_ROWS as AttnArgs;
+// kmask [B][Sk_cap] nullable.  At most 1536 keys (xattn_map_supported; xattn_map returns -1 beyond and launches nothing).  Deterministic:
+// a row's bits depend on its own Q row and its image's K and mask only.
+struct XattnMapArgs {
+    const uint16_t* Q;
+    const uint16_t* K;
+    int B, H, Sq, Sk, Sq_cap, Sk_cap;
+    const uint8_t* kmask;
+    int accumulate;
+    float scale;
+    float* scratch;
+};
+size_t xattn_map_scratch_bytes(int B, int Sq, int Sk);
+bool xattn_map_supported(int Sk);
+int xattn_map(const XattnMapArgs& a, mgStream_t stream);
+// scratch -> out [B][Sq][M_e1 + L + P]: key c < M_e1 is e1 slot c; column M_e1 + s is encoder output position s of the documented
+// [text L | patches P] order = key M_pad + workspace row (text_len [B] nullable: per-image padding semantics, workspace rows
+// [text Lb | patches P | text padding]).  Sk = M_pad + L + P.  Rows with qmask[b * qmask_ld + q] == 0 are 0.0 (qmask nullable).
+struct XattnGatherArgs {
+    const float* scratch;
+    float* out;
+    int B, Sq, Sk, M_e1, M_pad, L, P;
+    const int* text_len;
+    const uint8_t* qmask;
+    int qmask_ld;
+};
+void xattn_map_gather(const XattnGatherArgs& g, mgStream_t stream);
+void attention_set_qt(int qt);  // encoder attention: 1 (default) one 32-query tile per wave, 8 waves; 2: two tiles per wave, 4 waves (same bits, measured slower; tests, A/B runs)
 
 // ---------------------------------------------------------------------------------------------
 // decode step (single query per live sequence)

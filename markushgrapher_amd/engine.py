@@ -33,6 +33,11 @@ class MgGenOpts(C.Structure):
     _fields_ = [("num_return", C.c_int), ("token_scores", C.c_void_p), ("seq_scores", C.c_void_p), ("beam_indices", C.c_void_p)]
 
 
+class MgAttrOpts(C.Structure):
+    """include/mgrapher.h mg_attr_opts: the inclusive decoder-layer range of mg_decoder_attribute."""
+    _fields_ = [("layer_first", C.c_int), ("layer_last", C.c_int)]
+
+
 class MgSampleOpts(C.Structure):
     """include/mgrapher.h mg_sample_opts: the options of mg_generate_sampled and mg_generate_stream_sampled."""
     _fields_ = [("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float), ("seed", C.c_uint64), ("stream_ids", C.c_void_p),
@@ -162,6 +167,9 @@ class Engine:
         L.mg_score_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         L.mg_decoder_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mg_attribute_workspace_bytes.argtypes = L.mg_score_workspace_bytes.argtypes
+        L.mg_decoder_attribute.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                           C.POINTER(MgAttrOpts), C.c_void_p]
         L.mg_generate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
                                   C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]
@@ -460,6 +468,66 @@ class Engine:
             return tuple(np.stack([o[k] for o in outs], 1) for k in range(3))
         import torch
         return tuple(torch.stack([o[k] for o in outs], 1) for k in range(3))
+
+    def _attr_sets(self, enc_args, e1, sets, layers):
+        """ONE mg_encode, then one mg_decoder_attribute per (decoder_input_ids, decoder_attention_mask or None) of `sets`, each [B, T]
+        -> ([map [B, T, M_e1 + L + P]], enc_mask [B, L + P])"""
+        sets = [(self.mem.asarray(d, np.int64), None if m is None else self.mem.asarray(m, np.uint8)) for d, m in sets]
+        if len(sets[0][0].shape) != 2:
+            raise ValueError("decoder_input_ids must be [B, T]")
+        B, T = (int(v) for v in sets[0][0].shape)
+        for d, m in sets:
+            if any(tuple(x.shape) != (B, T) for x in (d, m) if x is not None):
+                raise ValueError(f"decoder_input_ids and decoder_attention_mask must all be [{B}, {T}] per candidate")
+        if int(enc_args[0].shape[0]) != B:
+            raise ValueError(f"decoder_input_ids are for {B} images, the encoder inputs for {int(enc_args[0].shape[0])}")
+        opts = None
+        if layers is not None:
+            first, last = (int(layers), int(layers)) if np.isscalar(layers) else (int(layers[0]), int(layers[1]))
+            opts = MgAttrOpts(first, last)
+        L = int(enc_args[0].shape[1])
+        M_e1 = int(e1.shape[1]) if e1 is not None else (self._e1_engine.out_tokens if getattr(self, "_e1_engine", None) is not None else 0)
+        need = C.c_size_t()
+        self._chk(self.lib.mg_attribute_workspace_bytes(self.model, B, L, T, M_e1, C.byref(need)))
+        if need.value > self._ws_bytes:                        # (before the encode: a workspace that moved has lost the encoder state)
+            self._ws = None
+            self._ws = self.mem.empty((need.value,), np.uint8)
+            self._ws_bytes = need.value
+        ws, nb = self._ws, self._ws_bytes
+        _, enc_mask = self.encode(*enc_args, T=T, e1=e1)
+        maps = []
+        for d, m in sets:
+            out = self.mem.empty((B, T, M_e1 + L + self.shape.num_patches), np.float32)
+            self._chk(self.lib.mg_decoder_attribute(self.model, self.mem.stream(), self.mem.ptr(ws), nb, self.mem.ptr(d),
+                                                    self.mem.ptr(m) if m is not None else None, B, T,
+                                                    C.byref(opts) if opts is not None else None, self.mem.ptr(out)))
+            maps.append(out)
+        return maps, enc_mask
+
+    def attribute(self, input_ids, bbox, attention_mask, pixel_values, decoder_input_ids, decoder_attention_mask=None, layers=None, e1=None):
+        """Where each decoder position looked (mg_decoder_attribute): the teacher-forced cross-attention softmax of the given sequences,
+        averaged over heads and the decoder layers `layers` = (first, last) inclusive (an int: that layer; None: all), formed on the chip
+        from the cross-attention launch's own Q / K - no [B, H, T, S] tensor exists.  -> map [B, T, M_e1 + L + P] f32 over
+        [e1 tokens | text slots | visual slots] and enc_mask [B, L + P] u8.  Unattended keys and rows with decoder_attention_mask == 0 are
+        exactly 0; every other row sums to 1."""
+        maps, enc_mask = self._attr_sets((input_ids, bbox, attention_mask, pixel_values), e1, [(decoder_input_ids, decoder_attention_mask)], layers)
+        return maps[0], enc_mask
+
+    def attribute_candidates(self, input_ids, bbox, attention_mask, pixel_values, decoder_input_ids, decoder_attention_mask=None, layers=None,
+                             e1=None):
+        """C given sequences per image: decoder_input_ids [B, C, T] (decoder_attention_mask [B, C, T] or None).  ONE mg_encode, then C
+        mg_decoder_attribute calls on its state.  -> map [B, C, T, M_e1 + L + P], enc_mask; candidate c equals attribute() of it alone,
+        bit for bit."""
+        if len(decoder_input_ids.shape) != 3:
+            raise ValueError("decoder_input_ids must be [B, C, T]")
+        dm = decoder_attention_mask
+        maps, enc_mask = self._attr_sets((input_ids, bbox, attention_mask, pixel_values), e1,
+                                         [(decoder_input_ids[:, c], None if dm is None else dm[:, c]) for c in range(int(decoder_input_ids.shape[1]))],
+                                         layers)
+        if isinstance(maps[0], np.ndarray):
+            return np.stack(maps, 1), enc_mask
+        import torch
+        return torch.stack(maps, 1), enc_mask
 
     def debug_decode_capture(self, capture_steps=0, rows=0, forced_ids=None):
         """Parity-test instrumentation (include/mgrapher.h mg_debug_decode_capture): returns the device buffer

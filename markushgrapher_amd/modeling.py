@@ -104,6 +104,57 @@ class ScoreOutput:
 
 
 @dataclass
+class AttributionOutput:
+    """attribute(): where in the page each output token came from - the decoder's cross-attention over the given sequences, averaged over
+    heads and the selected layers, computed on the device without the [B, H, T, S] probabilities.  T rows per sequence ([B, T, ..] or
+    [B, C, T, ..]); row t explains the token the decoder wrote after reading decoder input t.
+      cross_attention  [.., T, M_e1 + L + P] over [e1 tokens | text slots | visual slots]; unattended keys and invalid rows are 0,
+                       every valid row sums to 1
+      valid            [.., T] bool: rows up to and including a sequence's first EOS (sequences=) / where the label is not -100 (labels=)
+      e1               [.., T, M_e1] the OCSR-branch tokens' share (None without the branch)
+      text             [.., T, L] the text / OCR-cell tokens' share
+      image            [.., T, g, g], g = image_size / patch_size: the page.  A kept patch's share, plus the share of every text token whose
+                       embedding received that patch's embedding (an attended token outside the target segment), at the patch's grid cell.
+                       image.sum((-1, -2)) + (share of the text tokens that received no patch) + e1.sum(-1) = 1 on valid rows"""
+    cross_attention: torch.Tensor
+    valid: torch.Tensor
+    e1: Optional[torch.Tensor]
+    text: torch.Tensor
+    image: torch.Tensor
+
+    def __getitem__(self, k):
+        return getattr(self, k)
+
+
+def patch_assignment(bbox, attention_mask, grid):
+    """The encoder's input assembly (stock modeling_udop.py:171-251) restated on bbox [B, L, 4]: -> (pts [B, L] the grid cell, row-major,
+    whose patch embedding a text token is offered; recv [B, L] bool, the tokens that actually receive it - attended and outside the target
+    segment, i.e. the mean of the box is neither 0 nor 1; keep [B, grid * grid] bool, the patches that stay as visual slots - every token
+    drops its cell, padded and target-segment tokens included)."""
+    bbox = bbox.float()
+    px = torch.clip(torch.floor((bbox[:, :, 0] + bbox[:, :, 2]) / 2.0 * grid).long(), 0, grid - 1)
+    py = torch.clip(torch.floor((bbox[:, :, 1] + bbox[:, :, 3]) / 2.0 * grid).long(), 0, grid - 1) * grid
+    pts = px + py
+    mean = bbox.to(torch.float64).mean(-1)
+    recv = ~((mean == 0.0) | (mean == 1.0))
+    if attention_mask is not None:
+        recv = recv & (attention_mask.to(bbox.device) != 0)
+    keep = torch.ones(bbox.shape[0], grid * grid, dtype=torch.bool, device=bbox.device)
+    keep.scatter_(1, pts, torch.zeros_like(pts, dtype=torch.bool))
+    return pts, recv, keep
+
+
+def pool_to_image(text, visual, pts, recv, keep, grid):
+    """text [B, R, L] and visual [B, R, P] shares -> [B, R, grid, grid]: visual slot j is the j-th kept patch in ascending grid order; a
+    receiving text token adds its share at its cell."""
+    B, R, P = visual.shape
+    slot = (keep.long().cumsum(1) - 1).clamp(min=0)                                  # kept patch -> its visual slot
+    img = visual.gather(2, slot[:, None, :].expand(B, R, P)) * keep[:, None, :].to(visual.dtype)
+    img = img.scatter_add(2, pts[:, None, :].expand(B, R, pts.shape[1]), text * recv[:, None, :].to(text.dtype))
+    return img.view(B, R, grid, grid)
+
+
+@dataclass
 class GenerateOutput:
     """generate(return_dict_in_generate=True): the fields of stock GenerateEncoderDecoderOutput / GenerateBeamEncoderDecoderOutput that
     this path fills, plus `token_scores`.
@@ -455,6 +506,66 @@ class MarkushgrapherForConditionalGeneration(nn.Module):
         if int(n) == 0:
             loss = loss * float("nan")                  # cross_entropy's mean over no position
         return ScoreOutput(token_logprobs=tok, sequence_logprobs=tok.sum(-1), loss=loss, argmax_ids=arg, argmax_logprobs=alp)
+
+    @torch.no_grad()
+    def attribute(self, input_ids, bbox, pixel_values, attention_mask=None, sequences=None, labels=None, decoder_input_ids=None, layers=None,
+                  e1=None):
+        """Where in the page each token of given sequences came from: the decoder's cross-attention under teacher forcing, averaged over
+        heads and the decoder layers `layers` (None: all; an int: that layer; (first, last): inclusive range) - what the reference's
+        `config.output_attentions = True` (core/common/begin.py:121) is for, reduced on the device (Engine.attribute) instead of stored
+        per layer and head.  Give exactly one of
+          sequences  what generate() returned: [B, T + 1] (or [B, C, T + 1]: n-best lists, samples) = start token, tokens, EOS, padding.
+                     Decoder inputs are sequences[..., :-1]; row t explains sequences[..., t + 1]; rows after a sequence's first EOS are
+                     invalid (a sequence without EOS is valid throughout)
+          labels     score()'s convention: [B, T] or [B, C, T], -100 = ignored (invalid row); decoder inputs default to _shift_right(labels)
+        -> AttributionOutput.  One encoder pass, one decoder pass per candidate.  generate() and forward() are unchanged.
+        Not built: maps from inside generate() / the queue forms, self-attention and encoder maps, per-head or per-layer outputs, rollout or
+        gradient-based attribution, the ChemicalOCR stage."""
+        if (sequences is None) == (labels is None):
+            raise ValueError("attribute() needs exactly one of sequences= and labels=")
+        nl = int(self.config.num_decoder_layers)
+        if layers is not None:
+            rng = (layers, layers) if isinstance(layers, int) else tuple(layers)
+            if len(rng) != 2 or not all(isinstance(v, int) for v in rng) or not 0 <= rng[0] <= rng[1] < nl:
+                raise ValueError(f"layers must be None, a layer index or (first, last) with 0 <= first <= last < {nl}, got {layers!r}")
+            layers = rng
+        self._check_e1(e1)
+        eng = self._eng()
+        dmask = None
+        if sequences is not None:
+            if decoder_input_ids is not None:
+                raise ValueError("decoder_input_ids goes with labels=; sequences= carries its own decoder inputs")
+            if sequences.dim() not in (2, 3) or sequences.shape[-1] < 2:
+                raise ValueError(f"sequences must be [B, T + 1] or [B, C, T + 1] with T >= 1, got {tuple(sequences.shape)}")
+            dec, out_tok = sequences[..., :-1], sequences[..., 1:]
+            ended = (out_tok == self.config.eos_token_id).long().cumsum(-1)
+            valid = (ended - (out_tok == self.config.eos_token_id).long()) == 0      # up to and including the first EOS
+            dmask = valid.to(torch.uint8)
+        else:
+            if labels.dim() not in (2, 3):
+                raise ValueError(f"labels must be [B, T] or [B, C, T], got {tuple(labels.shape)}")
+            dec = self._shift_right(labels) if decoder_input_ids is None else decoder_input_ids
+            if tuple(dec.shape) != tuple(labels.shape):
+                raise ValueError("decoder_input_ids and labels must have the same shape")
+            valid = labels != -100
+        dec = dec.contiguous()
+        if dec.dim() == 3:
+            amap, enc_mask = eng.attribute_candidates(input_ids, bbox, attention_mask, pixel_values, dec,
+                                                      None if dmask is None else dmask.contiguous(), layers=layers, e1=e1)
+        else:
+            amap, enc_mask = eng.attribute(input_ids, bbox, attention_mask, pixel_values, dec, dmask, layers=layers, e1=e1)
+        if isinstance(amap, np.ndarray):                    # (an engine over a host backend hands back arrays)
+            amap = torch.from_numpy(amap)
+        valid = valid.to(amap.device)
+        if dmask is None:                                  # labels: every position is a decoder position, as in forward(); ignored rows -> 0
+            amap = amap * valid[..., None].to(amap.dtype)
+        B, L = int(input_ids.shape[0]), int(input_ids.shape[1])
+        g = int(self.config.image_size) // int(self.config.patch_size)
+        M = int(amap.shape[-1]) - L - g * g
+        text, vis = amap[..., M:M + L], amap[..., M + L:]
+        pts, recv, keep = patch_assignment(bbox.to(amap.device), attention_mask, g)
+        image = pool_to_image(text.reshape(B, -1, L), vis.reshape(B, -1, g * g), pts, recv, keep, g).view(*amap.shape[:-1], g, g)
+        return AttributionOutput(cross_attention=amap, valid=valid, e1=amap[..., :M] if M > 0 else None, text=text, image=image)
 
     def _default_mask(self, input_ids, attention_mask):
         if attention_mask is not None:
